@@ -7,7 +7,12 @@ image tiles dealt round-robin over the N ranks, slabs all-gathered over RCCL and
 rank 0. Scene and camera are resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5] [--nan-cull]
+                    [--full] [--dump-outputs DIR]
         (N > 1: bench.py starts the N ranks itself, one process per GPU, RCCL world N)
+        A plain run sets up, warms up, times the K steps and prints the result line. --full adds what
+        takes runs of its own: the counting-build pass (work per sample, phase split, lane utilisation,
+        roofline) and the CPU baseline. --dump-outputs DIR writes the last timed step's image as
+        DIR/image.npy (float32; a fixed seeded pixel sample when the frame exceeds DUMP_MAX_BYTES).
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU; --gpus must equal N)
 """
 import argparse
@@ -173,6 +178,28 @@ def pmc_valu(args):
     return out
 
 
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: larger frames are sampled down to this many bytes
+DUMP_SEED = 1024
+
+
+def dump_arrays(image):
+    """What --dump-outputs writes for the H x W x 3 RGB8 image of the last timed step: {"image": float32
+    H x W x 3}, or, when that exceeds DUMP_MAX_BYTES, the n x 3 values of a fixed sample of pixels
+    (DUMP_SEED, sorted flat indices, the same for every run of the same frame size)."""
+    h, w, c = image.shape
+    n = DUMP_MAX_BYTES // (4 * c)
+    if h * w <= n:
+        return {"image": image.astype(np.float32)}
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=n, replace=False))
+    return {"image": image.reshape(h * w, c)[idx].astype(np.float32)}
+
+
+def dump_outputs(directory, image):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in dump_arrays(image).items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def sample_chunk(pixels, spp):
     """rt_sample_chunk (include/rt.h): samples per tier-B work-item."""
     fill = (pixels * spp + (1 << 20) - 1) >> 20
@@ -308,14 +335,21 @@ def main():
                     help="CPU baseline threads (default: the affinity CPU count, capped by OMP_NUM_THREADS)")
     ap.add_argument("--cpu-spp", type=int, default=0,
                     help="spp cap of the bounded CPU sample (default min(spp, 40M/(W*H)); a probe sizes the sample to ~10 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-work", action="store_true", help="skip the counting-build pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the counting-build pass (work per sample, roofline) "
+                         "and the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's image as DIR/image.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-work", action="store_true", help="with --full: skip the counting-build pass")
     ap.add_argument("--traffic-json", default="",
                     help="PMC summary (scripts/pmc_summary.py) of this config's render kernel; default "
                          "profiles/r<latest>_pmc_<config>.json when the run uses the default kernel selection")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL over xGMI, default) or gloo (rehearsal: host-staged gather)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N without a launcher: start N ranks (one process per GPU) before anything touches the GPU
     try:
@@ -365,7 +399,7 @@ def main():
                          assemble=device_assembler(ctx, stream.cuda_stream))
 
     # device-measured work of this exact launch (counting build, outside the timed region)
-    work = ctx.render_work(cam, p) if not args.no_work else None
+    work = ctx.render_work(cam, p) if args.full and not args.no_work else None
     work_loop = ctx.last_launch()["loop"] if work else None  # (the counting build's walk: 2 = 4-wide, 1 = binary / mixed)
 
     for i in range(args.warmup):
@@ -406,6 +440,8 @@ def main():
         value = samples_frame * args.steps / elapsed / 1e6
         ms_per_step = elapsed / args.steps * 1e3
         img = image.cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, img)
         out = {
             "metric": "Msamples/s (WxHxspp/s) + achieved HBM GB/s, final scene 1200x800x500spp",
             "value": round(value, 3),
@@ -428,7 +464,7 @@ def main():
         }
         cb = None
         counters = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is timed at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg is timed at N=1 only
             if not args.cpu_spp:
                 args.cpu_spp = max(1, min(cfg["spp"], round(40e6 / (cfg["W"] * cfg["H"]))))
             threads, cores = cpu_threads(args)

@@ -86,7 +86,7 @@ def run_leg(leg, a):
             a.bench.split() if a.bench else [])
     else:
         cmd = [sys.executable, "-u", "bench.py", "--steps", str(a.steps), "--warmup", "1", "--no-cpu-baseline"] + (
-            [] if a.work else ["--no-work"]) + a.bench.split()
+            ["--full"] if a.work else []) + a.bench.split()
     t0 = time.time()
     r = subprocess.run(cmd, cwd=d, env=env, capture_output=True, text=True, timeout=a.timeout)
     if r.returncode:

@@ -15,6 +15,7 @@ for c in "${cfgs[@]}"; do
     c5) b="--config c5 --steps 1 --warmup 1"; s="--config c5 --steps 1 --warmup 0";;
     *)  b="--config $c --steps 2 --warmup 1"; s="--config $c --steps 1 --warmup 0";;
   esac
+  b="--full $b"  # (the bench line's roofline, work-per-sample and CPU-baseline sections are behind --full)
   steps+=(stats_$c 300 "cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $PWD/gpurun_out/stats_$c -o $c -- python3 $PWD/bench.py $s --no-cpu-baseline --no-work"
           pmc_$c 900 "scripts/pmc_passes.sh gpurun_out/pmc_$c --config $c && python scripts/pmc_summary.py gpurun_out/pmc_$c profiles/${tag}_pmc_$c.json && cp profiles/${tag}_pmc_$c.json gpurun_out/"
           bench_$c 600 "python -u bench.py $b > gpurun_out/${tag}_bench_$c.json")

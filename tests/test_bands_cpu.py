@@ -65,3 +65,17 @@ def test_cpu_baseline_threads_follow_affinity(monkeypatch):
     assert n == min(3, len(os.sched_getaffinity(0))) and c["nproc"] == os.cpu_count()
     monkeypatch.delenv("OMP_NUM_THREADS")
     assert bench.cpu_threads(A())[0] == len(os.sched_getaffinity(0))
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the cap is written whole as float32; a larger one as the same
+    seeded pixel sample every time, within the cap."""
+    img = (np.arange(40 * 30 * 3) % 251).astype(np.uint8).reshape(30, 40, 3)
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, img)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1200)  # 100 pixels of the 1200
+    s1, s2 = bench.dump_arrays(img)["image"], bench.dump_arrays(img)["image"]
+    assert s1.shape == (100, 3) and s1.nbytes <= 1200 and np.array_equal(s1, s2)
+    flat = {tuple(px) for px in img.reshape(-1, 3)}
+    assert all(tuple(px) in flat for px in s1.astype(np.uint8))
