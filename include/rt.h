@@ -501,6 +501,109 @@ typedef struct rt_launch_info {
 int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
 
 /*
+ * Progressive tier-B frames: the image of rt_render, rendered a few sample chunks at a time.
+ * A frame holds the running per-pixel sums of the chunks rendered so far (RT_RNG_PHILOX above: chunk
+ * sums added in chunk order from 0), so that a caller can look at the image while it converges, stop
+ * when it is good enough, or save the sums and finish the frame later. A frame advanced to its end in
+ * any step pattern resolves to the bytes and the linear image of rt_render with the same params.
+ *
+ * open     Tier B only (RT_RNG_EXACT: RT_E_UNSUPPORTED, a column's stream is one serial chain). The
+ *          frame is the whole image (shard_rank / shard_count are ignored, as in rt_render); on a
+ *          multi-device ctx it acts on the first device. The chunk size is fixed here:
+ *          CH = rt_sample_chunk(width*height, spp), chunks_total = ceil(spp / CH). The frame owns its
+ *          running sums (device memory, 24 bytes per pixel of the tile-padded image); the chunk sums
+ *          of a launch, the tail buffer and the work counter stay the ctx's. rt_render,
+ *          rt_render_shard_async and the debug entries may be called on the ctx between two advances:
+ *          they neither disturb the frame nor change their own results. Several frames may be open.
+ * advance  Renders the next min(max_chunks, remaining) chunks in chunk order and adds their sums to the
+ *          running sums, the same additions in the same order as rt_render makes. *out_chunks_done_now
+ *          (may be NULL) = chunks rendered by this call; 0 on a complete frame is not an error. A step
+ *          whose chunk sums exceed the per-launch bound is split into launches as a whole frame is.
+ *          Asynchronous: returns once the launches are queued; resolve and save drain them.
+ * resolve  The image over the samples rendered so far: per pixel sum / samples_done, then
+ *          albedoToColor; on a complete frame, rt_render's output bit for bit. out_rgb8 (H*W*3 bytes),
+ *          out_linear (H*W*3 doubles) and out may each be NULL: a null image pointer skips that copy,
+ *          so stats alone are a cheap poll. RT_E_STATE before the first chunk is rendered.
+ * stats    chunk = CH; chunks_total; chunks_done; samples_done = min(spp, chunks_done * CH);
+ *          kernel_ms = HIP-event time of the render launches queued since the last resolve;
+ *          nan_pixels = image pixels whose running sum has a NaN channel (permanent: the reference's
+ *          Lambertian-mixture quirk; their bytes stay 0); bytes_changed = 8-bit channels that differ
+ *          from the previous resolve of this frame (the first resolve of an opened or restored frame
+ *          compares with an all-zero image): the stopping rule of an 8-bit output is "the bytes
+ *          stopped moving". Both counts are exact.
+ * lifetime rt_upload_scene[_ex] on the ctx invalidates its open frames: their advance, resolve and
+ *          save return RT_E_STATE, close still works. rt_destroy closes the frames still open (their
+ *          handles are dead afterwards).
+ * save     The frame as a blob (below), with rt_write_ppm's buffer protocol: *out_len = bytes
+ *          required; the blob is written when cap >= *out_len (buf NULL or a short cap: size query).
+ * restore  A new frame from a blob, continuing exactly where the saved one stopped. RT_E_INVALID for
+ *          a malformed blob (rt_frame_blob_info's checks), RT_E_STATE when the ctx has no scene or
+ *          its scene's fingerprint or upload flags differ from the blob's.
+ *
+ * Blob layout, little-endian, RT_FRAME_BLOB_HEADER = 288 bytes of header, then the payload:
+ *     0  8 bytes  magic "RTFRAME\0"
+ *     8  u32      blob version (RT_FRAME_BLOB_VERSION = 1)
+ *    12  u32      upload flags of the scene (rt_upload_scene_ex)
+ *    16  48 bytes rt_render_params: i32 width, height, spp, max_depth, rng_mode; u32 flags; u64 seed;
+ *                 i32 tile, shard_rank, shard_count, _pad
+ *    64 192 bytes rt_camera: 24 f64 in declaration order
+ *   256  i32      CH
+ *   260  i32      chunks_done
+ *   264  i64      pixel count (width * height)
+ *   272  u64      scene fingerprint: 64-bit FNV-1a over the bytes of the caller's node, material,
+ *                 texture, perlin, image and image-pool arrays, then world_root, lights_root (i32)
+ *                 and background (3 f64) of the rt_scene_desc uploaded
+ *   280  u64      payload bytes = pixel count * 24
+ *   288  payload  the running sums, 3 f64 per pixel, image order (top row first)
+ * rt_frame_blob_info checks, on the host alone: the length covers the header; magic; version; width,
+ * height, spp positive (spp at most 2^31 - 1 - RT_CHUNK_MAX), max_depth >= 0, rng_mode
+ * RT_RNG_PHILOX, tile 0 or a multiple of 8 in [8, 256]; pixel count = width * height < 2^32;
+ * CH = rt_sample_chunk(pixels, spp); 0 <= chunks_done <= chunks_total; payload bytes = pixels * 24;
+ * length = 288 + payload bytes. Else RT_E_INVALID.
+ *
+ * Not covered: sharded or multi-device frames, per-pixel error estimates, adaptive sampling, and
+ * extending a frame past its spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its per-chunk meaning.
+ */
+#define RT_FRAME_BLOB_VERSION 1u
+#define RT_FRAME_BLOB_HEADER 288
+typedef struct rt_frame rt_frame;
+typedef struct rt_frame_stats {
+    int32_t chunk;
+    int32_t chunks_total;
+    int32_t chunks_done;
+    int32_t samples_done;
+    double kernel_ms;
+    int64_t nan_pixels;
+    int64_t bytes_changed;
+} rt_frame_stats; /* 40 bytes */
+typedef struct rt_frame_blob_desc {
+    uint32_t version;
+    uint32_t upload_flags;
+    rt_render_params params;
+    rt_camera camera;
+    int32_t chunk;
+    int32_t chunks_total;
+    int32_t chunks_done;
+    int32_t samples_done;
+    int64_t pixels;
+    uint64_t scene_fingerprint;
+    uint64_t payload_bytes;
+} rt_frame_blob_desc; /* 288 bytes */
+int rt_frame_open(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, rt_frame** out);
+int rt_frame_advance(rt_frame* f, int max_chunks, int* out_chunks_done_now);
+int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb8, double* out_linear, rt_frame_stats* out);
+int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len);
+int rt_frame_restore(rt_ctx* ctx, const void* buf, size_t len, rt_frame** out);
+int rt_frame_blob_info(const void* buf, size_t len, rt_frame_blob_desc* out);
+void rt_frame_close(rt_frame* f);
+/* The fingerprint rt_upload_scene records for a descriptor (host only; the blob's field at 272). */
+int rt_scene_fingerprint(const rt_scene_desc* desc, uint64_t* out);
+/* The chunking of a tier-B frame of `pixels` pixels at `spp` samples (host only): *out_chunk =
+ * rt_sample_chunk(pixels, spp), *out_chunks_total = ceil(spp / chunk). For callers that cannot use the
+ * header's inline (other languages): one rule, this header's. */
+int rt_frame_chunking(int64_t pixels, int spp, int* out_chunk, int* out_chunks_total);
+
+/*
  * Debug / parity entry: closest hit of n world rays (7 doubles each: origin, direction, time)
  * in [tmin, tmax]. out: 12 doubles per ray: hit(0/1), t, p xyz, normal xyz, u, v, front_face,
  * material. Media draws use tier-B stream (seed, pixel_id = ray index, sample 0).

@@ -856,6 +856,63 @@ __global__ void assemble(const T* slabs, T* image, int W, int H, int tile, int t
   image[i * 3 + 2] = slabs[src * 3 + 2];
 }
 
+// ---------------------------------------------------------------- progressive frames (rt_frame_*)
+// Image pixel -> its slot in an unsharded slab (assemble's map at shards = 1).
+__device__ __forceinline__ long long frame_slot(long long i, int W, int tile, int tiles_x) {
+  const int row = (int)(i / W), px = (int)(i % W);
+  const long long lt = (long long)(row / tile) * tiles_x + (px / tile);
+  const int bpr = tile >> 3;
+  const int bx = (px % tile) >> 3, by = (row % tile) >> 3;
+  return lt * tile * tile + (by * bpr + bx) * 64 + (row & 7) * 8 + (px & 7);
+}
+
+// A frame's preview: the running sums (A.acc, slab order) over `samples` samples, averaged and stored as
+// combine_chunks' last batch stores them (divide, store_pixel), in image order: A.out_rgb / A.out_lin are
+// the frame's H*W*3 image buffers (out_lin may be null). A.out_rgb still holds the previous preview:
+// counts[0] += pixels whose sum has a NaN channel, counts[1] += bytes that change. One pass; the counts
+// are reduced over each wave with ballots, over the block's 4 waves through LDS, and leave the block as
+// one atomic per counter.
+__global__ void __launch_bounds__(256) frame_resolve(RenderArgs A, int samples, unsigned long long* counts) {
+  __shared__ unsigned wave_nan[4], wave_chg[4];
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool nan = false, c0 = false, c1 = false, c2 = false;
+  if (i < (long long)A.W * A.H) {
+    const V3 sum = vload(A.acc + frame_slot(i, A.W, A.tile, A.tiles_x) * 3);
+    nan = sum.x != sum.x || sum.y != sum.y || sum.z != sum.z;
+    const V3 avg = divide(sum, (double)samples);
+    const uint8_t p0 = A.out_rgb[i * 3 + 0], p1 = A.out_rgb[i * 3 + 1], p2 = A.out_rgb[i * 3 + 2];
+    store_pixel(A, i, avg);
+    c0 = scale_color(avg.x) != p0;
+    c1 = scale_color(avg.y) != p1;
+    c2 = scale_color(avg.z) != p2;
+  }
+  const unsigned n_nan = (unsigned)__popcll(__ballot(nan));
+  const unsigned n_chg = (unsigned)(__popcll(__ballot(c0)) + __popcll(__ballot(c1)) + __popcll(__ballot(c2)));
+  if ((threadIdx.x & 63) == 0) {
+    wave_nan[threadIdx.x >> 6] = n_nan;
+    wave_chg[threadIdx.x >> 6] = n_chg;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned bn = wave_nan[0] + wave_nan[1] + wave_nan[2] + wave_nan[3];
+    const unsigned bc = wave_chg[0] + wave_chg[1] + wave_chg[2] + wave_chg[3];
+    if (bn) atomicAdd(&counts[0], (unsigned long long)bn);
+    if (bc) atomicAdd(&counts[1], (unsigned long long)bc);
+  }
+}
+
+// Saved sums (image order) back into a frame's slab-order running sums: assemble<double>'s inverse at
+// shards = 1 (rt_frame_restore; the slab's padding pixels are never read).
+__global__ void __launch_bounds__(256) frame_scatter(const double* image, double* sums, int W, int H, int tile,
+                                                     int tiles_x) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)W * H) return;
+  const long long dst = frame_slot(i, W, tile, tiles_x);
+  sums[dst * 3 + 0] = image[i * 3 + 0];
+  sums[dst * 3 + 1] = image[i * 3 + 1];
+  sums[dst * 3 + 2] = image[i * 3 + 2];
+}
+
 // ---------------------------------------------------------------- debug: closest hits
 template <unsigned F>
 __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* rays, int n, double tmin,

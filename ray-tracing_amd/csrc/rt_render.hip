@@ -25,6 +25,7 @@
 #include <numeric>
 #include <vector>
 
+#include "rt_frame_blob.h"
 #include "rt_kernels.h"
 #include "rt_prepare.h"
 
@@ -91,6 +92,43 @@ struct rt_ctx {
   };
   FrameBuf fb_slab, fb_slab_lin, fb_gather, fb_gather_lin, fb_img, fb_img_lin, fb_gens;
   int allocs = 0;  // hipMalloc calls made on this device by the current rt_render (rt_frame_timing)
+  // Progressive frames open on this ctx (rt_frame_*), and what a saved frame records of the scene: the
+  // fingerprint of the caller's descriptor and the upload flags (rt_frame_blob.cpp)
+  std::vector<rt_frame*> frames;
+  uint64_t fingerprint = 0;
+  uint32_t upload_flags = 0;
+};
+
+// A progressive frame (rt.h): the running per-pixel sums of the chunks rendered so far, in the slab
+// order of an unsharded launch, and the image-order buffers of its previews. All its work is queued on
+// the ctx's stream.
+struct rt_frame {
+  rt_ctx* ctx = nullptr;
+  bool valid = true;  // false once the ctx's scene was replaced
+  rt_camera cam{};
+  rt_render_params p{};
+  int chunk = 0, chunks_total = 0, chunks_done = 0;
+  long long slab = 0, npx = 0;
+  double* d_sum = nullptr;   // [slab pixel][3]
+  uint8_t* d_rgb = nullptr;  // the last preview's bytes (zero before the first), H*W*3
+  double* d_lin = nullptr;   // the last linear preview, H*W*3
+  double* d_stage = nullptr; // save's and restore's image-order copy of the sums, H*W*3, on first use
+  unsigned long long* d_counts = nullptr;  // frame_resolve's {nan_pixels, bytes_changed}
+  rt_frame_stats last{};     // the last resolve's counts (a poll with nothing new rendered repeats them)
+  // one event pair per advance since the last resolve (kernel_ms); `used` of them are pending
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  size_t used = 0;
+};
+
+// The chunks one launch_philox call renders. Default: the whole frame, folded through the ctx's d_acc
+// into the stored image. A progressive frame renders `count` chunks from `first` and keeps the running
+// sums in its own buffer.
+struct ChunkSpan {
+  int first = 0;
+  int count = -1;           // -1: every chunk of the frame
+  double* acc = nullptr;    // running sums between launches; nullptr: the ctx's d_acc, grown on demand
+  bool keep = false;        // keep the running sums in `acc` after the last chunk (no image is stored)
+  hipEvent_t ev_begin = nullptr, ev_end = nullptr;  // around the render launches; nullptr: the ctx's ev0 / ev1
 };
 
 namespace {
@@ -320,7 +358,7 @@ uint32_t cull(const rt_ctx* c, uint32_t flags) { return flags | (c->far_boxes ? 
 
 int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int rank, int shards, uint8_t* d_rgb,
                   double* d_lin, hipStream_t st, unsigned long long* d_work = nullptr,
-                  unsigned long long* d_prof = nullptr) {
+                  unsigned long long* d_prof = nullptr, const ChunkSpan& span = ChunkSpan{}) {
   RenderArgs A{};
   A.S = c->scene;
   A.cam = *cam;
@@ -360,7 +398,12 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   // kPartialCap bytes (RTAMD_PARTIAL_CAP overrides, for tests): a frame with more chunks renders them
   // in batches of consecutive chunks, one launch each, and combine_chunks folds each batch into a
   // running per-pixel sum in chunk order — the sum rt.h defines, whatever the batching.
-  const int chunks_total = A.chunks;
+  // (the span: the whole frame, or a progressive frame's next chunks)
+  const int frame_chunks = A.chunks;
+  const int span_first = span.first;
+  const int chunks_total = span.count < 0 ? frame_chunks : span.count;  // chunks of this call
+  if (span_first < 0 || chunks_total < 1 || span_first + chunks_total > frame_chunks) return invalid("bad chunk span");
+  hipEvent_t ev_begin = span.ev_begin ? span.ev_begin : c->ev0, ev_end = span.ev_end ? span.ev_end : c->ev1;
   const size_t per_chunk = (size_t)slab * 3 * sizeof(double);
   size_t cap = kPartialCap;
   if (const char* pc = std::getenv("RTAMD_PARTIAL_CAP")) cap = (size_t)std::max(1ll, std::atoll(pc));
@@ -368,7 +411,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   const int batches = (chunks_total + per_batch - 1) / per_batch;
   {
     const size_t need = (size_t)per_batch * per_chunk;
-    const size_t need_acc = batches > 1 ? per_chunk : 0;
+    const size_t need_acc = (batches > 1 && !span.acc) ? per_chunk : 0;
     if (need > c->partial_bytes || need_acc > c->acc_bytes) {
       HIPCHK(hipEventSynchronize(c->ev_done));
       if (need > c->partial_bytes) {
@@ -389,7 +432,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
       }
     }
     A.partial = c->d_partial;
-    A.acc = c->d_acc;
+    A.acc = span.acc ? span.acc : c->d_acc;
   }
   // The frame's tail (the full variants' replacement loop, kTail in rt_kernels.h; set below with the
   // loop): the last `tail_items` work-items of each launch are dealt one sample per unit, their colours
@@ -415,17 +458,19 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
       c->tail_bytes = need_tail;
     }
     A.tail_buf = c->d_tail;
-    for (int k0 = 0; k0 < chunks_total; k0 += per_batch) {
-      const int nk = std::min(per_batch, chunks_total - k0);
+    for (int b0 = 0; b0 < chunks_total; b0 += per_batch) {
+      const int nk = std::min(per_batch, chunks_total - b0);
+      const int k0 = span_first + b0;  // the launch's first chunk of the frame
       A.chunk_base = k0;
       A.chunks = nk;
       A.items_total = slab * nk;
       A.tail_start = A.items_total - std::min(A.items_total, tail_items);
       A.work_total = units_of(A.items_total);
       A.div_tile = make_udiv((uint32_t)(A.tile * A.tile * nk));
-      A.combine = (k0 > 0 ? 1 : 0) | (k0 + nk == chunks_total ? 2 : 0);
+      const bool last = b0 + nk == chunks_total;
+      A.combine = (k0 > 0 ? 1 : 0) | (last && !span.keep ? 2 : 0);
       HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), st));
-      if (k0 == 0) HIPCHK(hipEventRecord(c->ev0, st));
+      if (b0 == 0) HIPCHK(hipEventRecord(ev_begin, st));
       HIPCHK(hipLaunchKernel(fn, grid, block, args, bytes, st));  // (arguments are copied at launch)
       HIPCHK(hipGetLastError());
       if (A.tail_start < A.items_total) {
@@ -435,7 +480,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
                                dim3(256), targs, 0, st));
         HIPCHK(hipGetLastError());
       }
-      if (A.combine & 2) HIPCHK(hipEventRecord(c->ev1, st));
+      if (last) HIPCHK(hipEventRecord(ev_end, st));
       const int rc = launch_combine(c, A, st);
       if (rc) return rc;
     }
@@ -781,6 +826,7 @@ int rt_last_frame_timing(rt_ctx* c, rt_frame_timing* out) {
 
 void rt_destroy(rt_ctx* c) {
   if (!c) return;
+  while (!c->frames.empty()) rt_frame_close(c->frames.back());  // (each close removes its frame)
   for (size_t r = 0; r < c->comms.size(); ++r) {
     if (!c->comms[r]) continue;
     DeviceGuard _dr(r == 0 ? c->device : c->peers[r - 1]->device);
@@ -881,6 +927,15 @@ int rt_upload_scene_ex(rt_ctx* c, const rt_scene_desc* din, uint32_t flags) {
   rt::PreparedScene P;
   int rc = rt::prepare_scene(din, flags, P);
   if (rc) return rc;
+  // the scene is replaced from here on: the ctx's open progressive frames are over (their queued work is
+  // drained first, it reads the scene about to be freed)
+  if (!c->frames.empty()) {
+    DEVICE_SCOPE(c->device);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (rt_frame* f : c->frames) f->valid = false;
+  }
+  c->fingerprint = rt::scene_fingerprint(din);
+  c->upload_flags = flags;
   rc = upload_prepared(c, P, din);
   for (size_t r = 0; r < c->peers.size() && !rc; ++r) rc = upload_prepared(c->peers[r], P, din);
   if (rc) {  // (a device failed: no device keeps a scene, so a multi-device render cannot mix two)
@@ -1102,6 +1157,249 @@ int rt_last_launch(rt_ctx* c, rt_launch_info* out) {
   if (!c || !out) return invalid("null argument");
   *out = c->last_launch;
   return RT_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ progressive frames (rt.h)
+namespace {
+
+int state_error(const std::string& s) {
+  rt::set_error(s);
+  return RT_E_STATE;
+}
+
+// A frame that may still be advanced, resolved and saved: its ctx holds the scene it was opened on.
+int frame_live(const rt_frame* f, const char* what) {
+  if (!f) return invalid(std::string(what) + ": null frame");
+  if (!f->valid || !f->ctx->has_scene)
+    return state_error(std::string(what) + ": the ctx's scene was replaced (or a launch failed) since the frame was opened");
+  return RT_OK;
+}
+
+// (the ctx's device is selected)
+void frame_free(rt_frame* f) {
+  (void)hipFree(f->d_sum);
+  (void)hipFree(f->d_rgb);
+  (void)hipFree(f->d_lin);
+  (void)hipFree(f->d_stage);
+  (void)hipFree(f->d_counts);
+  for (auto& e : f->events) {
+    (void)hipEventDestroy(e.first);
+    (void)hipEventDestroy(e.second);
+  }
+  delete f;
+}
+
+// A frame of `p` on c with zero sums and a zero previous preview, registered on the ctx.
+int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, const char* what, rt_frame** out) {
+  rt_render_params p = *pin;  // whole image: the shard fields are ignored
+  p.shard_rank = 0;
+  p.shard_count = 1;
+  int rc = check_params(&p);
+  if (rc) return rc;
+  if (p.rng_mode != RT_RNG_PHILOX)
+    return unsupported(std::string(what) + ": progressive frames are tier B (RT_RNG_PHILOX) only");
+  if (std::getenv("RTAMD_CHUNK")) return unsupported(std::string(what) + ": RTAMD_CHUNK overrides rt.h's chunk size");
+  if (!c->has_scene) return state_error(std::string(what) + ": no scene uploaded");
+  DEVICE_SCOPE(c->device);
+  rt_frame* f = new rt_frame();
+  f->ctx = c;
+  f->cam = *cam;
+  f->p = p;
+  int tile, tiles_x;
+  long long tt, ps;
+  geometry(&p, tile, tiles_x, tt, ps, f->slab);
+  f->npx = (long long)p.width * p.height;
+  f->chunk = rt_sample_chunk((int64_t)f->npx, p.spp);
+  f->chunks_total = (p.spp + f->chunk - 1) / f->chunk;
+  f->last.chunk = f->chunk;
+  f->last.chunks_total = f->chunks_total;
+  f->last.chunks_done = -1;  // (no resolve yet)
+  auto init = [&]() -> int {
+    const size_t sums = sizeof(double) * 3 * (size_t)f->slab, img = (size_t)f->npx * 3;
+    HIPCHK(hipMalloc((void**)&f->d_sum, sums));
+    HIPCHK(hipMalloc((void**)&f->d_rgb, img));
+    HIPCHK(hipMalloc((void**)&f->d_lin, sizeof(double) * img));
+    HIPCHK(hipMalloc((void**)&f->d_counts, 2 * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(f->d_sum, 0, sums, c->stream));
+    HIPCHK(hipMemsetAsync(f->d_rgb, 0, img, c->stream));
+    return RT_OK;
+  };
+  if ((rc = init())) {
+    frame_free(f);
+    return rc;
+  }
+  c->frames.push_back(f);
+  *out = f;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_frame_open(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, rt_frame** out) {
+  if (!c || !cam || !p || !out) return invalid("rt_frame_open: null argument");
+  *out = nullptr;
+  return frame_new(c, cam, p, "rt_frame_open", out);
+}
+
+int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
+  if (out_now) *out_now = 0;
+  int rc = frame_live(f, "rt_frame_advance");
+  if (rc) return rc;
+  if (max_chunks < 0) return invalid("rt_frame_advance: max_chunks must not be negative");
+  const int n = std::min(max_chunks, f->chunks_total - f->chunks_done);
+  if (n == 0) return RT_OK;  // (a complete frame: nothing left to render)
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  if (f->used == f->events.size()) {
+    hipEvent_t a = nullptr, b = nullptr;
+    HIPCHK(hipEventCreate(&a));
+    if (hipError_t e = hipEventCreate(&b)) {
+      (void)hipEventDestroy(a);
+      return hip_fail(e, "hipEventCreate");
+    }
+    f->events.emplace_back(a, b);
+  }
+  ChunkSpan span;
+  span.first = f->chunks_done;
+  span.count = n;
+  span.acc = f->d_sum;
+  span.keep = true;
+  span.ev_begin = f->events[f->used].first;
+  span.ev_end = f->events[f->used].second;
+  rc = launch_philox(c, &f->cam, &f->p, 0, 1, nullptr, nullptr, c->stream, nullptr, nullptr, span);
+  if (rc) {  // (some of the step's launches may have been folded in: the sums are no longer a frame's)
+    f->valid = false;
+    return rc;
+  }
+  ++f->used;
+  f->chunks_done += n;
+  if (out_now) *out_now = n;
+  return RT_OK;
+}
+
+int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb, double* out_lin, rt_frame_stats* out) {
+  int rc = frame_live(f, "rt_frame_resolve");
+  if (rc) return rc;
+  if (f->chunks_done == 0) return state_error("rt_frame_resolve: no chunk rendered yet");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  // (nothing rendered since the last resolve: the device still holds that preview, and its stats repeat)
+  if (f->last.chunks_done != f->chunks_done) {
+    RenderArgs A{};
+    A.W = f->p.width;
+    A.H = f->p.height;
+    long long tt, ps, slab;
+    geometry(&f->p, A.tile, A.tiles_x, tt, ps, slab);
+    A.acc = f->d_sum;
+    A.out_rgb = f->d_rgb;
+    A.out_lin = f->d_lin;
+    int samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
+    unsigned long long* d_counts = f->d_counts;
+    HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    void* args[] = {&A, &samples, &d_counts};
+    HIPCHK(hipLaunchKernel((const void*)frame_resolve, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), args, 0,
+                           c->stream));
+    HIPCHK(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};  // (copied in stream order: one wait for the kernel and the counts)
+    HIPCHK(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    double ms = 0.0;
+    for (size_t i = 0; i < f->used; ++i) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, f->events[i].first, f->events[i].second));
+      ms += t;
+    }
+    f->used = 0;
+    f->last.chunks_done = f->chunks_done;
+    f->last.samples_done = samples;
+    f->last.kernel_ms = ms;
+    f->last.nan_pixels = (int64_t)counts[0];
+    f->last.bytes_changed = (int64_t)counts[1];
+  }
+  if (out_rgb) HIPCHK(hipMemcpy(out_rgb, f->d_rgb, (size_t)f->npx * 3, hipMemcpyDeviceToHost));
+  if (out_lin) HIPCHK(hipMemcpy(out_lin, f->d_lin, sizeof(double) * (size_t)f->npx * 3, hipMemcpyDeviceToHost));
+  if (out) *out = f->last;
+  return RT_OK;
+}
+
+int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len) {
+  int rc = frame_live(f, "rt_frame_save");
+  if (rc) return rc;
+  const size_t payload = sizeof(double) * 3 * (size_t)f->npx;
+  const size_t need = RT_FRAME_BLOB_HEADER + payload;
+  if (out_len) *out_len = need;
+  if (!buf || cap < need) return RT_OK;  // (size query)
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  rt_frame_blob_desc b{};
+  b.version = RT_FRAME_BLOB_VERSION;
+  b.upload_flags = c->upload_flags;
+  b.params = f->p;
+  b.camera = f->cam;
+  b.chunk = f->chunk;
+  b.chunks_done = f->chunks_done;
+  b.pixels = f->npx;
+  b.scene_fingerprint = c->fingerprint;
+  b.payload_bytes = payload;
+  rt::blob_write_header(b, (uint8_t*)buf);
+  // the sums in image order (assemble's map at one shard), staged on the device, then copied out
+  static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the blob's payload is copied as the host's doubles");
+  if (!f->d_stage) HIPCHK(hipMalloc((void**)&f->d_stage, payload));  // (kept: a checkpoint per step allocates once)
+  int tile, tiles_x;
+  long long tt, ps, slab;
+  geometry(&f->p, tile, tiles_x, tt, ps, slab);
+  hipLaunchKernelGGL(assemble<double>, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
+                     (const double*)f->d_sum, f->d_stage, f->p.width, f->p.height, tile, tiles_x, 1, slab);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy((uint8_t*)buf + RT_FRAME_BLOB_HEADER, f->d_stage, payload, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_frame_restore(rt_ctx* c, const void* buf, size_t len, rt_frame** out) {
+  if (!c || !out) return invalid("rt_frame_restore: null argument");
+  *out = nullptr;
+  rt_frame_blob_desc b;
+  int rc = rt_frame_blob_info(buf, len, &b);
+  if (rc) return rc;
+  if (!c->has_scene) return state_error("rt_frame_restore: no scene uploaded");
+  if (b.scene_fingerprint != c->fingerprint || b.upload_flags != c->upload_flags)
+    return state_error("rt_frame_restore: the blob was saved over another scene (fingerprint or upload flags differ)");
+  rt_frame* f = nullptr;
+  if ((rc = frame_new(c, &b.camera, &b.params, "rt_frame_restore", &f))) return rc;
+  auto fill = [&]() -> int {
+    DEVICE_SCOPE(c->device);
+    HIPCHK(hipMalloc((void**)&f->d_stage, (size_t)b.payload_bytes));
+    HIPCHK(hipMemcpy(f->d_stage, (const uint8_t*)buf + RT_FRAME_BLOB_HEADER, (size_t)b.payload_bytes, hipMemcpyHostToDevice));
+    int tile, tiles_x;
+    long long tt, ps, slab;
+    geometry(&f->p, tile, tiles_x, tt, ps, slab);
+    hipLaunchKernelGGL(frame_scatter, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
+                       (const double*)f->d_stage, f->d_sum, f->p.width, f->p.height, tile, tiles_x);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return RT_OK;
+  };
+  if ((rc = fill())) {
+    rt_frame_close(f);
+    return rc;
+  }
+  f->chunks_done = b.chunks_done;
+  *out = f;
+  return RT_OK;
+}
+
+void rt_frame_close(rt_frame* f) {
+  if (!f) return;
+  rt_ctx* c = f->ctx;
+  DeviceGuard _dg(c->device);
+  (void)hipStreamSynchronize(c->stream);  // (its queued launches write its buffers)
+  c->frames.erase(std::remove(c->frames.begin(), c->frames.end(), f), c->frames.end());
+  frame_free(f);
 }
 
 int rt_debug_closest_hits(rt_ctx* c, const double* rays, int n, double tmin, double tmax, uint64_t seed,

@@ -122,6 +122,20 @@ class rt_render_params(C.Structure):
                 ("shard_rank", C.c_int32), ("shard_count", C.c_int32), ("_pad", C.c_int32)]
 
 
+class rt_frame_stats(C.Structure):
+    _fields_ = [("chunk", C.c_int32), ("chunks_total", C.c_int32), ("chunks_done", C.c_int32),
+                ("samples_done", C.c_int32), ("kernel_ms", C.c_double), ("nan_pixels", C.c_int64),
+                ("bytes_changed", C.c_int64)]
+
+
+class rt_frame_blob_desc(C.Structure):
+    _fields_ = [("version", C.c_uint32), ("upload_flags", C.c_uint32), ("params", rt_render_params),
+                ("camera", rt_camera), ("chunk", C.c_int32), ("chunks_total", C.c_int32), ("chunks_done", C.c_int32),
+                ("samples_done", C.c_int32), ("pixels", C.c_int64), ("scene_fingerprint", C.c_uint64),
+                ("payload_bytes", C.c_uint64)]
+
+
+assert C.sizeof(rt_frame_stats) == 40 and C.sizeof(rt_frame_blob_desc) == 288
 assert C.sizeof(rt_node) == 64 and C.sizeof(rt_material) == 16 and C.sizeof(rt_texture) == 48
 assert C.sizeof(rt_perlin) == 9216 and C.sizeof(rt_camera) == 192 and C.sizeof(rt_render_params) == 48
 assert C.sizeof(rt_scene_desc) == 112
@@ -140,6 +154,8 @@ EXPORTED = [
     "rt_wide_bvh", "rt_tree_stack_need", "rt_last_launch", "rt_write_pfm", "rt_debug_probe",
     "rt_prepare_scene", "rt_render_step_profile", "rt_create_multi", "rt_ctx_devices", "rt_last_frame_timing",
     "rt_debug_exact_trace", "rt_quantize_wide",
+    "rt_frame_open", "rt_frame_advance", "rt_frame_resolve", "rt_frame_save", "rt_frame_restore",
+    "rt_frame_blob_info", "rt_frame_close", "rt_scene_fingerprint", "rt_frame_chunking",
 ]
 
 # include/rt_wide.h: one 4-wide node (128 B)
@@ -228,6 +244,15 @@ def lib() -> C.CDLL:
             "rt_ctx_devices": (I, [C.c_void_p, P(I), P(I), I]),
             "rt_last_frame_timing": (I, [C.c_void_p, P(rt_frame_timing)]),
             "rt_debug_exact_trace": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(U64), I, P(D), I, P(I)]),
+            "rt_frame_open": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(C.c_void_p)]),
+            "rt_frame_advance": (I, [C.c_void_p, I, P(I)]),
+            "rt_frame_resolve": (I, [C.c_void_p, P(C.c_uint8), P(D), P(rt_frame_stats)]),
+            "rt_frame_save": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_size_t)]),
+            "rt_frame_restore": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_void_p)]),
+            "rt_frame_blob_info": (I, [C.c_char_p, C.c_size_t, P(rt_frame_blob_desc)]),
+            "rt_frame_close": (None, [C.c_void_p]),
+            "rt_scene_fingerprint": (I, [P(rt_scene_desc), P(U64)]),
+            "rt_frame_chunking": (I, [C.c_int64, I, P(I), P(I)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -503,6 +528,26 @@ def make_params(width, height, spp, max_depth, rng_mode=RT_RNG_PHILOX, seed=1024
     return p
 
 
+def frame_chunking(pixels: int, spp: int) -> Tuple[int, int]:
+    """rt_frame_chunking: (samples per chunk, chunks) of a tier-B frame, by include/rt.h's own
+    rt_sample_chunk (the C rule, not a copy of it)."""
+    ch, n = C.c_int(0), C.c_int(0)
+    _check(lib().rt_frame_chunking(int(pixels), int(spp), C.byref(ch), C.byref(n)), "rt_frame_chunking")
+    return ch.value, n.value
+
+
+def sample_chunk(pixels: int, spp: int) -> int:
+    """rt_sample_chunk (include/rt.h), evaluated by the library: samples per tier-B chunk of a frame."""
+    return frame_chunking(pixels, spp)[0]
+
+
+def scene_fingerprint(scene: "Scene") -> int:
+    """rt_scene_fingerprint: what a saved progressive frame records of the scene it was rendered over."""
+    out = C.c_uint64(0)
+    _check(lib().rt_scene_fingerprint(C.byref(scene.desc), C.byref(out)), "rt_scene_fingerprint")
+    return out.value
+
+
 def device_count() -> int:
     n = C.c_int(0)
     _check(lib().rt_device_count(C.byref(n)), "rt_device_count")
@@ -557,6 +602,15 @@ class Context:
         _check(lib().rt_upload_scene_ex(self._h, C.byref(scene.desc), RT_UPLOAD_REFERENCE_BVH if reference_bvh else 0),
                "rt_upload_scene")
         self._scene = scene
+
+    def open_frame(self, cam: rt_camera, params: rt_render_params) -> "ProgressiveFrame":
+        """rt_frame_open: a progressive tier-B frame of this ctx's scene (rtamd.progressive)."""
+        return ProgressiveFrame.open(self, cam, params)
+
+    def restore_frame(self, blob: bytes) -> "ProgressiveFrame":
+        """rt_frame_restore: the frame a `ProgressiveFrame.save` blob holds, to be continued on this ctx
+        (which must hold the scene the blob was saved over)."""
+        return restore_frame(self, blob)
 
     def render(self, cam: rt_camera, params: rt_render_params, col_gens: Optional[np.ndarray] = None,
                linear: bool = False, want_gens: bool = False):
@@ -788,3 +842,6 @@ def assemble_host(slabs: np.ndarray, params: rt_render_params) -> np.ndarray:
         ok = m >= 0
         img[m[ok]] = slabs[r][ok]
     return img.reshape(H, W, 3)
+
+
+from .progressive import ProgressiveFrame, blob_info, render_progressive, restore_frame  # noqa: E402
