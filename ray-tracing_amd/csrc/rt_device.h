@@ -92,18 +92,11 @@ constexpr bool kSL = (F & F_SLIBM) != 0;
 #else
 #define RT_COLD(c) (c)
 #endif
-// The IEEE division of the rare operands. RT_DIV_CALL=1 puts it out of line, one copy per kernel instead of
-// one per inlined quotient (the C4 kernel inlines 157 IEEE divisions, ~1.9 k of its 14.1 k instructions, and
-// its 83.5 KB of code miss the instruction cache: 102 M misses per launch, profiles/r6_pmc_c4.json); the call
-// raised its scratch 176 -> 192 B/lane (round 6), so it stays inline.
-#ifndef RT_DIV_CALL
-#define RT_DIV_CALL 0
-#endif
-#if RT_DIV_CALL
-__device__ __noinline__ double ieee_div(double a, double b) { return a / b; }
-#else
+// The IEEE division of the rare operands, inline: the C4 kernel inlines 157 of them (~1.9 k of its 14.1 k
+// instructions, and its 83.5 KB of code miss the instruction cache: 102 M misses per launch,
+// profiles/r6_pmc_c4.json), but out of line, one copy per kernel, the call raised its scratch 176 -> 192
+// B/lane (round 6).
 __device__ __forceinline__ double ieee_div(double a, double b) { return a / b; }
-#endif
 __device__ __forceinline__ bool in_range(double x) {
   const double ax = fabs(x);
   return (ax >= 0x1p-900) & (ax <= 0x1p900);

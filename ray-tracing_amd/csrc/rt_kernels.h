@@ -3,9 +3,6 @@
 // variant's render kernels (so the variants compile in parallel), rt_render.hip the small kernels
 // and the host half of the C ABI. Kernel design: DESIGN.md §3.
 #pragma once
-#ifndef RT_LANE_LDS
-#define RT_LANE_LDS 1
-#endif
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,7 +11,6 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "rt.h"
@@ -383,49 +379,9 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES) render_philox_lds(RenderAr
 // ended and starts their next segment (or sample, or pixel), then steps every walking lane one
 // node at a time until at most trav_stop/64 of the live lanes are still walking. Lanes never
 // wait for the slowest walk of their wave, and shading runs for many lanes at once.
-// The replacement loop's per-segment throughput and per-chunk sum: in registers, or (kStateLds: the compact
-// LDS-staged spheres kernel, RT_STATE_LDS) in the lane's LDS slots, so that they are not live across the
-// walk — the 4-wave kernel spilled them to scratch.
-// RT_STATE_LDS: 1 throughput and sum, 2 the throughput only, 0 neither. The compact form's parts are
-// separable for A/B runs: RT_COMPACT_STACK16 (16-bit stacks), RT_COMPACT_SLEAF (32-byte sphere leaves).
-#ifndef RT_STATE_LDS
-#define RT_STATE_LDS 1
-#endif
-#ifndef RT_COMPACT_STACK16
-#define RT_COMPACT_STACK16 1
-#endif
-#ifndef RT_COMPACT_SLEAF
-#define RT_COMPACT_SLEAF 1
-#endif
 template <unsigned F>
-constexpr bool kStateLds = RT_STATE_LDS != 0 && (F & F_SLEAF) != 0;
-template <unsigned F>
-constexpr bool kSumLds = RT_STATE_LDS == 1 && (F & F_SLEAF) != 0;
-// LDS bytes per lane the compact form keeps its state in
-constexpr int kStateLdsBytes = RT_STATE_LDS == 1 ? 48 : (RT_STATE_LDS == 2 ? 24 : 0);
-template <bool LDS>
-struct LaneV3 {
-  V3 r;
-  double* p;
-  int stride;
-  __device__ __forceinline__ V3 get() const {
-    if constexpr (LDS) return v3(p[0], p[stride], p[2 * stride]);
-    return r;
-  }
-  __device__ __forceinline__ void set(V3 v) {
-    if constexpr (LDS) {
-      p[0] = v.x;
-      p[stride] = v.y;
-      p[2 * stride] = v.z;
-    } else {
-      r = v;
-    }
-  }
-};
-
-template <unsigned F, class STK>
-__device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S, STK* stk, int stride, int* side_p,
-                                             volatile uint32_t* wq, double* st = nullptr) {
+__device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S, int* stk, int stride, int* side_p,
+                                             volatile uint32_t* wq) {
   const int lane = threadIdx.x & 63;
   const unsigned long long lanes_below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
@@ -452,14 +408,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
   int& depth = kLaneLds ? ex[3 * stride] : l_depth;
   px = 0, row = 0, s_end = 0, depth = 0;
   int s = 0;
-  // (st: the lane's 6 LDS doubles, `stride` apart: throughput xyz, then the chunk's sum xyz)
-  LaneV3<kStateLds<F>> thr{v3(0, 0, 0), st, stride};
-  LaneV3<kSumLds<F>> sum{v3(0, 0, 0), st + 3 * (kSumLds<F> ? stride : 0), stride};
-  // (RT_LEAF_Q: the 4-wide walk's queue word sits below the lane's stack, rt_trace.h trav_postpone)
-  if constexpr (RT_LEAF_Q && (F & F_WIDE) != 0) {
-    stk[0] = (STK)-1;
-    stk += stride;
-  }
+  V3 thr = v3(0, 0, 0), sum = v3(0, 0, 0);  // the segment's throughput, the chunk's sum
   RngPhilox g;
   g.init(A.seed, 0, 0);
   Trav t;  // the segment's ray lives only here between segments (no second copy is carried)
@@ -475,8 +424,8 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
       ++samples;
     }
     if (A.flags & RT_FLAG_NAN_ZERO) contrib = nan_zero(contrib);
-    const V3 sm = sum.get() + contrib;
-    sum.set(sm);
+    const V3 sm = sum + contrib;
+    sum = sm;
     ++s;
     const bool all_nan = (A.flags & RT_FLAG_NAN_CULL) && sm.x != sm.x && sm.y != sm.y && sm.z != sm.z;
     if (s == s_end || all_nan) {
@@ -486,7 +435,9 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
       w = -1;
     }
   };
-  auto all_nan3 = [](V3 a) __attribute__((always_inline)) { return a.x != a.x && a.y != a.y && a.z != a.z; };
+  // (by reference: by value the compiler promotes `thr` to registers before inlining and numbers the loop's
+  // values in another order — the same code with the registers permuted, and a kernel that was not timed)
+  auto all_nan3 = [](const V3& a) __attribute__((always_inline)) { return a.x != a.x && a.y != a.y && a.z != a.z; };
 
   for (;;) {
     unsigned long long s0 = 0;
@@ -500,10 +451,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
     // already: its colour is NaN whichever leaf the reference's order picks (NaN * anything, including
     // the background's 0, is NaN), and a tier-B sample's draws reach no other sample. (NaN-t hits come
     // from the Lambertian quirk's +x ray in a box top's plane, whose pdf is 0 / 0: DESIGN.md §4.3.)
-    // hoisted media, taken at the end of a first walk (RT_MEDIA_AFTER; rt_trace.h media_after)
-    if constexpr ((F & F_MEDIA) != 0)
-      if (ready && !t.redo) media_after<F>(S, t, kEps, cnt, g, side);
-    if (ready && (t.tie || (kRefMixed<F> && t.lite)) && !t.redo && !all_nan3(thr.get())) {
+    if (ready && (t.tie || (kRefMixed<F> && t.lite)) && !t.redo && !all_nan3(thr)) {
       ready = false;
       if constexpr ((F & F_COUNT) != 0) ++cnt.ties;
       trav_redo<F>(t, S.world_ref, INFINITY);
@@ -522,13 +470,13 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
       Ray ray = plain(t.ray);  // (every frame has closed: the world ray again)
       const bool got = trav_finish<F>(S, t, ray, kEps, h, side);
       V3 contrib;
-      V3 th = thr.get();
+      V3 th = thr;
       if (shade_hit<F>(S, got, h, ray, th, depth, g, contrib, cnt)) {
         end_sample(contrib);
       } else if (depth <= 0) {  // rayColor's d <= 0 -> black (thr * 0 keeps a NaN throughput NaN)
         end_sample(vmul(th, v3(0.0, 0.0, 0.0)));
       } else {  // next segment of the same path
-        thr.set(th);
+        thr = th;
         t.ray.o = ray.o;
         t.ray.d = ray.d;
         t.ray.tm = ray.tm;
@@ -577,7 +525,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
             done = true;
           } else if (kTail<F> ? work_unit(A, (uint32_t)wi, px, row, s, s_end, w)
                               : work_item(A, (uint32_t)wi, px, row, s, s_end, w)) {
-            sum.set(v3(0, 0, 0));
+            sum = v3(0, 0, 0);
           } else {
             w = -1;
           }
@@ -601,7 +549,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
       t.ray.o = cray.o;
       t.ray.d = cray.d;
       t.ray.tm = cray.tm;
-      thr.set(v3(1.0, 1.0, 1.0));
+      thr = v3(1.0, 1.0, 1.0);
       depth = A.max_depth;
       if (depth <= 0) {
         end_sample(vmul(v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0)));
@@ -614,8 +562,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
       trav_begin<F>(t, plain(t.ray), S.world, kEps, INFINITY);
       // worlds with media or frames: the reference's order over the re-bounded skeleton
       if (S.ref_walk) trav_restart_ref(t, S.world, INFINITY);
-      trav_media_first<F>(S, t, kEps, cnt, g, side);  // (hoisted media: RT_BVH_MEDIA_FIRST, RT_MEDIA_AFTER=0)
-      t.node = media_rest<F>(S, t.node);               // (RT_MEDIA_AFTER: they are taken when the walk ends)
+      trav_media_first<F>(S, t, kEps, cnt, g, side);  // (hoisted media: RT_BVH_MEDIA_FIRST)
       walking = true;
     }
     if (!walking) break;  // this lane is finished; the rest of the wave carries on without it
@@ -659,7 +606,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
 // LDS ints per lane of a kernel: the traversal stack, then (instance frames possible) Side slots
 template <unsigned F>
 constexpr int lane_ints() {
-  return ((F & F_W8) ? 2 * RT_WSTACK : ((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK)) + ((F & F_FRAMES) ? kSideInts : 0);
+  return ((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK) + ((F & F_FRAMES) ? kSideInts : 0);
 }
 
 // Global-memory replacement loop: the lane stacks (and Side slots) in dynamic LDS sized by the host
@@ -686,15 +633,7 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES)
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   __shared__ uint32_t wave_q[WAVES * 4][2];  // (static: kStaticLds bytes ahead of the dynamic LDS)
   constexpr int rec = (F & F_WIDE) ? (int)sizeof(rt_wnode) : (int)sizeof(rt_node);
-  // The compact form (F_SLEAF, round 6; spheres-only worlds): the leaf table staged as the leaves' 32-byte
-  // sphere quadruples (Scene::sleaves; the 64-byte records stay in global memory for trav_finish, once per
-  // segment), 16-bit lane stacks (the staged tree's node ids, leaf slots and — in tie redos — the flat ids
-  // of a world whose tree fits the LDS all fit 15 bits, and an F_WIDE kernel masks a flat id's kind tags off
-  // anyway), and the lanes' throughput and chunk sums in LDS (kStateLds): VERDICT r5 item 3.
-  constexpr bool kCompact = (F & F_SLEAF) != 0;
-  constexpr bool kSleaf = kCompact && RT_COMPACT_SLEAF;
-  constexpr int lrec = kSleaf ? 32 : (int)sizeof(rt_node);
-  using STK = typename std::conditional<kCompact && RT_COMPACT_STACK16, short, int>::type;
+  constexpr int lrec = (int)sizeof(rt_node);
   {
     const uint4* src = (F & F_WIDE) ? reinterpret_cast<const uint4*>(A.S.wnodes)
                                     : reinterpret_cast<const uint4*>(A.S.nodes);
@@ -702,7 +641,7 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES)
     const int n16 = n_nodes * (rec / 16);
     for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
     // F_WIDE: the leaf table too, when it fits (n_leaves > 0)
-    const uint4* lsrc = kSleaf ? reinterpret_cast<const uint4*>(A.S.sleaves) : reinterpret_cast<const uint4*>(A.S.leaves);
+    const uint4* lsrc = reinterpret_cast<const uint4*>(A.S.leaves);
     uint4* ldst = reinterpret_cast<uint4*>(lds + (size_t)n_nodes * rec);
     const int l16 = n_leaves * (lrec / 16);
     for (int i = threadIdx.x; i < l16; i += blockDim.x) ldst[i] = lsrc[i];
@@ -711,22 +650,15 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES)
   Scene S = A.S;
   if constexpr ((F & F_WIDE) != 0) S.wnodes = reinterpret_cast<const rt_wnode*>(lds);
   else S.nodes = reinterpret_cast<const rt_node*>(lds);
-  if constexpr (kSleaf) S.sleaves = reinterpret_cast<const double*>(lds + (size_t)n_nodes * rec);
-  else if constexpr (LEAF_LDS) S.leaves = reinterpret_cast<const rt_node*>(lds + (size_t)n_nodes * rec);
+  if constexpr (LEAF_LDS) S.leaves = reinterpret_cast<const rt_node*>(lds + (size_t)n_nodes * rec);
   else n_leaves = 0;
   constexpr int lanes = WAVES * 256;
   unsigned char* lane_base = lds + (size_t)n_nodes * rec + (size_t)n_leaves * lrec;
-  STK* stk = reinterpret_cast<STK*>(lane_base) + threadIdx.x;
+  int* stk = reinterpret_cast<int*>(lane_base) + threadIdx.x;
   // (per lane: stack_entries stack entries, then side_ints_of Side slots, then lane_lds_of's 4 lane ints —
-  // launch_philox sizes the dynamic LDS with the same helpers — and for kStateLds 6 doubles after them)
-  int* side_p = reinterpret_cast<int*>(lane_base + (size_t)stack_entries * lanes * sizeof(STK)) + threadIdx.x;
-  double* st = nullptr;
-  if constexpr (kStateLds<F>) {
-    const int side_total = side_ints_of(F, S.frames, 2) + (lane_lds_of(F, 2) ? 4 : 0);
-    st = reinterpret_cast<double*>(lane_base + (size_t)stack_entries * lanes * sizeof(STK) +
-                                   (size_t)side_total * lanes * sizeof(int)) + threadIdx.x;
-  }
-  philox_loop2<F>(A, S, stk, lanes, side_p, wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], st);
+  // launch_philox sizes the dynamic LDS with the same helpers)
+  int* side_p = reinterpret_cast<int*>(lane_base + (size_t)stack_entries * lanes * sizeof(int)) + threadIdx.x;
+  philox_loop2<F>(A, S, stk, lanes, side_p, wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
 }
 
 // The tail's work-items (work_unit): each chunk's sample colours added in sample order from 0, as the
@@ -919,13 +851,7 @@ __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* 
                                                          double tmax, uint64_t seed, int joint, int walk, double* out) {
   __shared__ int stk_mem[(lane_ints<F>() + 1) * RT_BLOCK];
   int* stk = &stk_mem[threadIdx.x];
-  Side side{&stk_mem[(((F & F_W8) ? 2 * RT_WSTACK : ((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK)) + 1) * RT_BLOCK +
-                     threadIdx.x],
-            RT_BLOCK};
-  if constexpr (RT_LEAF_Q && (F & F_WIDE) != 0) {  // (the leaf queue word below the stack)
-    stk[0] = -1;
-    stk += RT_BLOCK;
-  }
+  Side side{&stk_mem[(((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK) + 1) * RT_BLOCK + threadIdx.x], RT_BLOCK};
   const int i = blockIdx.x * RT_BLOCK + threadIdx.x;
   if (i >= n) return;
   const double* q = rays + 7 * (long long)i;
@@ -943,10 +869,8 @@ __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* 
     trav_begin<F>(t, r, S.world, tmin, tmax);
     if (S.ref_walk) trav_restart_ref(t, S.world, tmax);  // (the re-bounded skeleton, mixed walk)
     trav_media_first<F>(S, t, tmin, cnt, g, side);        // (hoisted media as the render loop takes them)
-    t.node = media_rest<F>(S, t.node);
     bool walking = true;
     walk_until<F>(S, t, walking, tmin, stk, RT_BLOCK, joint != 0, 0, 0, cnt, g, side);
-    media_after<F>(S, t, tmin, cnt, g, side);
     if (t.tie || (kRefMixed<F> && t.lite)) {
       trav_redo<F>(t, S.world_ref, tmax);
       while (trav_step<F>(S, t, tmin, stk, RT_BLOCK, joint != 0, cnt, g, side)) {
@@ -1065,26 +989,13 @@ __global__ void math_probe(int op, const double* x, const double* y, int n, doub
 // sample per lane walk, 1 = ray replacement over the binary tree, 2 = replacement over the
 // 4-wide tree.
 template <unsigned V>
-const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false, bool w8 = false) {
-  if constexpr (V == (kVarSpheres | F_WIDE)) {
-    if (!lds && w8) {  // (the 8-wide tree as record pairs, from global memory: A/B)
-      if (w == 2) return (const void*)render_philox2<V | F_W8, 2>;
-      if (w == 4) return (const void*)render_philox2<V | F_W8, 4>;
-      return (const void*)render_philox2<V | F_W8, 3>;
-    }
-  }
+const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false) {
   if constexpr (V == (kVarSpheres | F_WIDE)) {
     if (!lds && q) {  // (the quantised tree and sphere quadruples from global memory)
       if (w == 2) return (const void*)render_philox2<V | F_QNODE, 2>;
       if (w == 3) return (const void*)render_philox2<V | F_QNODE, 3>;
       if (w == 4) return (const void*)render_philox2<V | F_QNODE, 4>;
       return (const void*)render_philox2<V | F_QNODE, 1>;
-    }
-  }
-  if constexpr (V == (kVarSpheres | F_WIDE)) {
-    if (lds && leaf_lds && q) {  // the compact LDS form: sphere quadruples, 16-bit stacks, state in LDS
-      if (w == 4) return (const void*)render_philox2_lds<V | F_SLEAF, 4, true>;
-      if (w == 3) return (const void*)render_philox2_lds<V | F_SLEAF, 3, true>;
     }
   }
   if constexpr ((V & F_WIDE) != 0) {
@@ -1106,16 +1017,15 @@ const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false, bool 
   return (const void*)render_philox2<V, 1>;
 }
 template <unsigned V>
-const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = false, bool w8 = false) {
+const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = false) {
   if (count) {
     if constexpr (V == kVarSpheres) {
-      if (loop == 2 && w8) return (const void*)render_philox2<V | F_WIDE | F_COUNT | F_W8, 1>;
       if (loop == 2 && q) return (const void*)render_philox2<V | F_WIDE | F_COUNT | F_QNODE, 1>;
     }
     if (loop == 2) return (const void*)render_philox2<V | F_WIDE | F_COUNT, 1>;
     return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
   }
-  if (loop == 2) return pick_w<V | F_WIDE>(lds, w, leaf_lds, q, w8);
+  if (loop == 2) return pick_w<V | F_WIDE>(lds, w, leaf_lds, q);
   if (loop == 1) return pick_w<V>(lds, w);
   if (lds) {
     if (w == 2) return (const void*)render_philox_lds<V, 2>;
@@ -1146,7 +1056,7 @@ const void* pick_full(int loop, bool lds, int w, bool count) {
 // Render-kernel tables, one per kernel translation unit: the kernel for (loop, LDS-staged?, waves per
 // SIMD, counting build?, leaf table in LDS?) of that unit's variant(s).
 namespace rt {
-const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q, bool w8);
+const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q);
 const void* philox_kernel_spheres_global(int w);  // rt_k_spheres_global.hip
 const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds);
 const void* philox_kernel_full(int loop, bool lds, int w, bool count);

@@ -4,9 +4,6 @@
 // copies the result to the device, and `make -C tests/c asan` builds it (with rt_bvh.cpp,
 // rt_scene.cpp, rt_scenes.cpp) under AddressSanitizer + UBSan for the malformed-descriptor tests.
 #include "rt_prepare.h"
-#ifndef RT_FRAME_BATCH
-#define RT_FRAME_BATCH 0
-#endif
 
 #include <algorithm>
 #include <cmath>
@@ -25,7 +22,6 @@ int rebuild_for_device(std::vector<rt_node>& nodes, int root);
 int unfold_media(std::vector<rt_node>& nodes, int root);
 bool build_wide_bvh(const std::vector<rt_node>& nodes, int root, std::vector<rt_wnode>& out, int* stack_need);
 bool quantize_wide(const std::vector<rt_wnode>& in, std::vector<rt_qnode>& out);
-bool build_wide8_bvh(const std::vector<rt_node>& nodes, int root, std::vector<rt_wnode>& out, int* stack_need);
 }  // namespace rt
 
 namespace rt {
@@ -201,16 +197,10 @@ void mixed_wide_trees(PreparedScene& P, const std::vector<rt_node>& host, const 
   const int n = (int)dev.size();
   if (n >= RT_WNODE) return;  // (ids must stay clear of the RT_WNODE tag)
   std::vector<int> roots;
-  // The top `bin` levels of each re-bounded subtree stay binary (exact fp64 box tests, RTAMD_MIXW_BIN,
-  // default 0): the 4-wide trees start below them. lvl: -1 outside re-bounded subtrees, else the binary
-  // levels above this node inside one; kIn: inside a 4-wide tree already.
-  const char* bin_env = std::getenv("RTAMD_MIXW_BIN");
-  const int bin = bin_env ? std::max(0, std::min(8, std::atoi(bin_env))) : 0;
-  constexpr int kIn = 1 << 20;
-  std::vector<char> seen((size_t)n * (bin + 3), 0);
-  auto is_bvh_at = [&](int id) { return (flat[id].type & RT_TYPE_MASK) == RT_NODE_BVH; };
-  std::function<void(int, int)> find = [&](int id, int lvl) {
-    const size_t key = (size_t)id * (bin + 3) + (size_t)(lvl < 0 ? 0 : (lvl >= kIn ? bin + 2 : 1 + std::min(lvl, bin)));
+  // Each re-bounded subtree's topmost ordered node roots a 4-wide tree. in: inside a 4-wide tree already.
+  std::vector<char> seen((size_t)n * 2, 0);
+  std::function<void(int, bool)> find = [&](int id, bool in) {
+    const size_t key = (size_t)id * 2 + (in ? 1 : 0);
     if (seen[key]) return;
     seen[key] = 1;
     const rt_node& x = flat[id];
@@ -218,26 +208,20 @@ void mixed_wide_trees(PreparedScene& P, const std::vector<rt_node>& host, const 
     if (ty == RT_NODE_BVH) {
       const bool ord = (x.c & RT_BVH_ORDERED) != 0;
       if (ord && (x.c & RT_BVH_MEDIA_FIRST)) {  // a hoisted medium (rt_bvh.cpp skeleton): in no 4-wide tree
-        find(x.b, lvl);
+        find(x.b, in);
         return;
       }
-      int next = lvl;
-      if (ord && lvl < kIn) {
-        const int here = lvl < 0 ? 0 : lvl;
-        if (here >= bin || !is_bvh_at(x.a) || !is_bvh_at(x.b)) {
-          roots.push_back(id);
-          next = kIn;
-        } else {
-          next = here + 1;
-        }
+      if (ord && !in) {
+        roots.push_back(id);
+        in = true;
       }
-      find(x.a, next);  // (frames inside re-bounded subtrees hold subtrees of their own)
-      find(x.b, next);
+      find(x.a, in);  // (frames inside re-bounded subtrees hold subtrees of their own)
+      find(x.b, in);
     } else if ((ty == RT_NODE_TRANSLATE || ty == RT_NODE_ROTATE) && !(x.type & RT_CHAIN_PRIM)) {
-      find(x.a, -1);  // a frame: its child starts a new region
+      find(x.a, false);  // a frame: its child starts a new region
     }
   };
-  find(world, -1);
+  find(world, false);
   if (roots.empty()) return;
   std::vector<rt_wnode> wide;
   std::vector<int> wroot(n, -1), wneed_root(n, 0);
@@ -268,13 +252,6 @@ void mixed_wide_trees(PreparedScene& P, const std::vector<rt_node>& host, const 
         fuse_frame(flat, wroot, leaves.back());
       }
       w.child[k] = ~slot[id];
-#if RT_FRAME_BATCH
-      // an instance frame's slot loses bit 26 (every walk decodes ~(x | RT_ISMED)), so that walk_until
-      // tells lanes at frames without a load
-      const int fty = flat[id].type & RT_TYPE_MASK;
-      if ((fty == RT_NODE_TRANSLATE || fty == RT_NODE_ROTATE) && !(flat[id].type & RT_CHAIN_PRIM))
-        w.child[k] &= ~RT_ISMED;
-#endif
     }
   // Stack bound of the mixed walk: skeleton nodes left first, re-bounded binary nodes either child
   // first, a frame one entry, a wide node up to 3 stacked siblings (wide_node writes 3 slots) above the
@@ -304,9 +281,7 @@ void mixed_wide_trees(PreparedScene& P, const std::vector<rt_node>& host, const 
     return memo[id] = r;
   };
   const int need = need_of(world);
-  // (+ 3: the walk's 2 entries of headroom, and one more for the leaf postponement's parked next node,
-  // rt_trace.h kMixPostpone; beyond that the binary walk's bound stays)
-  if (need + 3 > RT_WSTACK) return;
+  if (need + 2 > RT_WSTACK) return;  // (the walk's 2 entries of headroom; beyond that the binary walk's bound stays)
   for (int r : roots) dev[r].c = RT_BVH_ORDERED | (dev[r].c & 3) | RT_WROOT | (wroot[r] << 2);
   P.wnodes = std::move(wide);
   P.leaves = std::move(leaves);
@@ -435,14 +410,8 @@ int prepare_scene(const rt_scene_desc* din, uint32_t flags, PreparedScene& P) {
   if (P.replace_ok && !P.ref_walk) {  // 4-wide fp32-box tree over the same world tree (unflagged node copy)
     std::vector<rt_wnode> wide;
     int need = 0;
-    // RTAMD_W8=1 (A/B only): spheres-only worlds get the 8-wide tree as record pairs (F_W8 kernels; walked
-    // from global memory, 4 entries of stack headroom)
-    const char* w8env = std::getenv("RTAMD_W8");
-    const bool w8 = w8env && w8env[0] == '1' && variant_for(P.features) == kVarSpheres;
-    if ((w8 ? (build_wide8_bvh(nodes, d->world_root, wide, &need) && need + 4 <= 2 * RT_WSTACK)
-            : (build_wide_bvh(nodes, d->world_root, wide, &need) && need + 3 <= RT_WSTACK)) &&
+    if (build_wide_bvh(nodes, d->world_root, wide, &need) && need + 3 <= RT_WSTACK &&
         (size_t)wide.size() < (size_t)INT32_MAX / 2) {
-      P.w8 = w8;
       // The walk's leaf table: the leaves the wide tree references, each copied once (a moving
       // sphere with its EXT record), with `c` = the flat node id; leaf references ~id become ~slot.
       std::vector<rt_node> leaves;
@@ -460,8 +429,7 @@ int prepare_scene(const rt_scene_desc* din, uint32_t flags, PreparedScene& P) {
           w.child[k] = ~slot[id];
         }
       // spheres-only worlds: the leaves' 32-byte sphere quadruples (centre, radius) beside the full
-      // records — the compact LDS-staged kernel stages them (round 6) — and, RTAMD_QNODE=1 (A/B only), the
-      // quantised nodes (rt_qnode) for the global-memory kernels. Measured on C5 at 100 spp, same box:
+      // records and, RTAMD_QNODE=1 (A/B only), the quantised nodes (rt_qnode) for the global-memory kernels. Measured on C5 at 100 spp, same box:
       // 1023 ms with 128-byte nodes, 1173 with quantised nodes (the plane decoding's VALU), 1030 with
       // only the 32-byte sphere leaves: the walk is not bound by the tree's footprint
       bool spheres = variant_for(P.features) == kVarSpheres;
@@ -472,7 +440,7 @@ int prepare_scene(const rt_scene_desc* din, uint32_t flags, PreparedScene& P) {
           for (int k = 0; k < 4; ++k) P.sleaves[4 * i + k] = leaves[i].f[k];
       }
       const char* qenv = std::getenv("RTAMD_QNODE");
-      if (w8 || !(spheres && qenv && qenv[0] == '1' && quantize_wide(wide, P.qnodes))) P.qnodes.clear();
+      if (!(spheres && qenv && qenv[0] == '1' && quantize_wide(wide, P.qnodes))) P.qnodes.clear();
       P.wnodes = std::move(wide);
       P.leaves = std::move(leaves);
       P.wide_stack_need = std::max(need, v.stack_need[unfolded]);

@@ -60,7 +60,6 @@ struct rt_ctx {
   int n_leaves = 0;
   int n_wnodes = 0;
   int wide_stack_need = 0;
-  bool w8 = false;           // the 4-wide arrays hold the 8-wide tree as record pairs (F_W8 kernels, A/B)
   bool rebuilt_bvh = false;
   bool far_boxes = false;    // a BVH box coordinate beyond 2^100: the walks take the per-axis box test (cull())
   bool mixed_wide = false;   // media / frame world with 4-wide trees over its re-bounded subtrees (F_MIXW)
@@ -230,7 +229,6 @@ void free_scene(rt_ctx* c) {
   c->d_qnodes = nullptr;
   c->d_sleaves = nullptr;
   c->mixed_wide = false;
-  c->w8 = false;
   c->n_leaves = 0;
   c->n_wnodes = 0;
   c->d_nodes = nullptr;
@@ -296,12 +294,11 @@ int waves_target(int dflt) {
   return (w >= 1 && w <= 4) ? w : dflt;
 }
 // (the render kernels live in one translation unit per variant: rt_k_*.hip)
-const void* philox_kernel(unsigned var, int loop, bool lds, int w, bool count, bool leaf_lds = false, bool q = false,
-                          bool w8 = false) {
+const void* philox_kernel(unsigned var, int loop, bool lds, int w, bool count, bool leaf_lds = false, bool q = false) {
   if (var == kVarSpheres) {
     // (the 4-wide tree from global memory, 128-byte nodes: its own unit, rt_k_spheres_global.hip)
-    if (loop == 2 && !lds && !count && !q && !w8 && !std::getenv("RTAMD_NO_COLD")) return rt::philox_kernel_spheres_global(w);
-    return rt::philox_kernel_spheres(loop, lds, w, count, leaf_lds, q, w8);
+    if (loop == 2 && !lds && !count && !q && !std::getenv("RTAMD_NO_COLD")) return rt::philox_kernel_spheres_global(w);
+    return rt::philox_kernel_spheres(loop, lds, w, count, leaf_lds, q);
   }
   if (var == kVarCornell) return rt::philox_kernel_cornell(loop, lds, w, count, leaf_lds);
   if (var == kVarFullDark) return rt::philox_kernel_full_dark(loop, lds, w, count);
@@ -553,37 +550,19 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   // variant on the replacement loop 3 (C4 at 100 spp: 90.9 vs 87.5 Msamples/s at 2), on the
   // per-sample loop 2 despite 784 B/lane of scratch (C4 35.2 vs 23.4 at 1 wave, 9.1 at 3)
   int waves = (var == kVarSpheres || loop) ? waves_target(3) : waves_target(is_full(var) ? 2 : 1);
-  // the mixed walk's leaf postponement (kMixPostpone, rt_trace.h) keeps a lane's next node on the stack
-  // while its parked leaf is tested (or its frame opened): one stack entry more
-  const int postpone = (loop == 1 && (var & F_MIXW) && RT_MIXW_POSTPONE) ? 1 : 0;
   // Side slots after the stacks, then the 4 lane ints philox_loop2 keeps in LDS (RT_LANE_LDS)
   const int side_ints = side_ints_of(var, c->scene.frames, loop) + (lane_lds_of(var, loop) ? 4 : 0);
   // LDS-staged kernel when the traversal's node array plus the stacks fit one CU's 160 KiB
   // (RTAMD_LDS=0 disables it for A/B runs).
-  if (!count && !env_off("RTAMD_LDS") && (!is_full(var) || loop) && !(wide && c->w8)) {  // (F_W8: global only)
-    const int entries = wide ? c->wide_stack_need + 3 + (RT_LEAF_Q ? 1 : 0) : c->stack_need + 2 + postpone;  // (wide_node writes 3 slots; + the leaf queue word)
+  if (!count && !env_off("RTAMD_LDS") && (!is_full(var) || loop)) {
+    const int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;  // (wide_node writes 3 slots)
     const int items = wide ? c->n_wnodes : c->n_nodes;
     const size_t rec = wide ? sizeof(rt_wnode) : sizeof(rt_node);
     const bool leaf_lds = wide && !env_off("RTAMD_LEAF_LDS");  // RTAMD_LEAF_LDS=0: leaves never in LDS
-    // The compact form of a spheres-only world's 4-wide kernel (F_SLEAF, rt_kernels.h render_philox2_lds):
-    // 32-byte sphere leaves, 16-bit lane stacks (ids below 2^15), the lanes' throughput and chunk sums in
-    // LDS. Opt-in (RTAMD_COMPACT=1): measured slower on C2
-    const char* ce = std::getenv("RTAMD_COMPACT");
-    const bool compact = var == kVarSpheres && wide && leaf_lds && waves >= 3 && c->d_sleaves && c->n_nodes < 32768 &&
-                         c->n_wnodes < 32768 && c->n_leaves <= 32768 && ce && ce[0] == '1';
-    constexpr size_t kStateBytes = kStateLdsBytes;
-    constexpr size_t kStackBytes = RT_COMPACT_STACK16 ? sizeof(short) : sizeof(int);
-    constexpr size_t kLeafBytes = RT_COMPACT_SLEAF ? 32 : sizeof(rt_node);
     // LDS bytes at `w` waves per SIMD: the nodes, the lane stacks, and the wide walk's leaf table
     // when it fits as well
     auto lds_bytes = [&](int w, int& n_leaves) {
-      if (compact) {
-        const size_t b = (size_t)items * rec + ((size_t)entries * kStackBytes + (size_t)side_ints * sizeof(int) +
-                                                kStateBytes) * (w * 256);
-        n_leaves = c->n_leaves;
-        return b + (size_t)n_leaves * kLeafBytes;
-      }
-      size_t b = (size_t)items * rec + (size_t)(entries + side_ints) * (w * 256) * sizeof(int);
+      const size_t b = (size_t)items * rec + (size_t)(entries + side_ints) * (w * 256) * sizeof(int);
       n_leaves = leaf_lds && b + (size_t)c->n_leaves * sizeof(rt_node) <= kLdsBudget ? c->n_leaves : 0;
       return b + (size_t)n_leaves * sizeof(rt_node);
     };
@@ -595,7 +574,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
     const int block = waves * 256;
     const size_t bytes = lds_bytes(waves, n_leaves);
     if (bytes <= kLdsBudget) {
-      const void* fn = philox_kernel(var, loop, true, waves, false, n_leaves > 0, compact);
+      const void* fn = philox_kernel(var, loop, true, waves, false, n_leaves > 0);
       HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
       int n_items = items;
       void* args[] = {&A, &n_items, (void*)&entries, &n_leaves};
@@ -607,11 +586,10 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   }
   // (spheres-only worlds uploaded with RTAMD_QNODE=1 read the 4-wide tree from global memory in its
   // 64-byte quantised form: A/B only, measured slower)
-  const void* fn = philox_kernel(var, loop, false, count ? 1 : waves, count, false, loop == 2 && c->d_qnodes,
-                                 loop == 2 && c->w8);
+  const void* fn = philox_kernel(var, loop, false, count ? 1 : waves, count, false, loop == 2 && c->d_qnodes);
   // replacement loops: lane stacks (+ Side slots) in dynamic LDS, sized for this world's stack bound
-  // (wide_node writes 3 slots, F_W8's farther half 4; + the leaf queue word)
-  int entries = wide ? c->wide_stack_need + (c->w8 ? 4 : 3) + (RT_LEAF_Q ? 1 : 0) : c->stack_need + 2 + postpone;
+  // (wide_node writes 3 slots)
+  int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;
   const size_t dyn = loop ? (size_t)(entries + side_ints) * RT_BLOCK * sizeof(int) : 0;
   if (loop) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
   int bpc = 1;
@@ -619,7 +597,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   const long long want = (A.work_total + RT_BLOCK - 1) / RT_BLOCK;
   const long long resident = (long long)c->cu_count * std::max(1, bpc);
   const int grid = (int)std::max(1ll, std::min(want, resident));
-  c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (count ? F_COUNT : 0u) | (loop == 2 && c->w8 ? F_W8 : 0u), loop, 0, 0,
+  c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (count ? F_COUNT : 0u), loop, 0, 0,
                                   count ? 1 : waves, grid, RT_BLOCK, (int)dyn, A.work_total, A.chunk,
                                   (loop == 2 || (loop == 1 && c->mixed_wide)) ? c->n_wnodes : 0, batches, 0};
   void* args[] = {&A, &entries};
@@ -901,7 +879,6 @@ int upload_prepared(rt_ctx* c, const rt::PreparedScene& P, const rt_scene_desc* 
   c->n_leaves = (int)P.leaves.size();
   c->stack_need = P.stack_need;
   c->wide_stack_need = P.wide_stack_need;
-  c->w8 = P.w8;
   c->rebuilt_bvh = P.rebuilt_bvh;
   // The division-free box test (rt_trace.h box_hit) reads an infinite slab product as the quotient; with
   // |origin| <= 2^100 (ray_safe) and |d| >= 2^-900 that holds while every finite box coordinate is within
@@ -1425,10 +1402,7 @@ int rt_debug_closest_hits(rt_ctx* c, const double* rays, int n, double tmin, dou
   const dim3 grid((n + RT_BLOCK - 1) / RT_BLOCK);
   if ((flags & RT_DEBUG_QNODE) && !c->d_qnodes)
     return unsupported("rt_debug_closest_hits: no quantised 4-wide tree for this world (spheres-only worlds)");
-  if ((flags & RT_DEBUG_WIDE) && c->w8)  // (the 8-wide pairs: spheres-only worlds)
-    hipLaunchKernelGGL(closest_hits<F_UV | F_WIDE | F_W8>, grid, dim3(RT_BLOCK), 0, c->stream, c->scene, d_rays, n,
-                       tmin, tmax, seed, joint, 1, d_out);
-  else if (flags & RT_DEBUG_QNODE)
+  if (flags & RT_DEBUG_QNODE)
     hipLaunchKernelGGL(closest_hits<F_UV | F_WIDE | F_QNODE>, grid, dim3(RT_BLOCK), 0, c->stream, c->scene, d_rays, n,
                        tmin, tmax, seed, joint, 1, d_out);
   else if (flags & RT_DEBUG_WIDE)

@@ -1,8 +1,5 @@
 // rt_trace.h — intersection, traversal, light sampling, textures and scattering (device).
 #pragma once
-#ifndef RT_FRAME_BATCH
-#define RT_FRAME_BATCH 0
-#endif
 #include "rt_device.h"
 
 namespace rtd {
@@ -307,37 +304,6 @@ __device__ __forceinline__ void cuboid_face(const rt_node* n, int i, int& plane,
   k = (i & 1) ? (plane == 0 ? z0 : (plane == 1 ? y0 : x0)) : (plane == 0 ? z1 : (plane == 1 ? y1 : x1));
 }
 
-// A cuboid the ray certainly misses within [t_min, t_max] (round 6): the joint slab interval of its box,
-// division-free as box_hit computes it, empty by a margin of 2^-40 of the magnitudes involved (the
-// quotients' and the faces' in-plane coordinates' roundings are ~2^-52 of them). Then no face can pass
-// rectHit (Lib.hs:1014-1028): at a face's t the ray lies in that face's plane, so another axis's slab must
-// exclude it, by more than the face test's rounding of that coordinate. Zero direction components give
-// +-inf products, exact (outside a slab it is parallel to: L = +inf or U = -inf, and that face pair's t are
-// +-inf, out of range); a NaN product (the origin on such a slab's plane), a NaN bound or a ray box_hit
-// cannot bound (ray_safe) decides nothing: the six faces decide. Rays that start on a box they are leaving
-// (a bounce off a box top) reach its leaf under the 4-wide test's slack and are the common case here.
-// Measured (round 6, A/B only): inlined into the walk it raised the C4 kernel's scratch 176 -> 288 B/lane and
-// C4 at 100 spp 146.9 -> 166.0 ms (C3 98.6 -> 99.9); out of line, 304 B/lane. Off.
-#ifndef RT_CUBOID_PRETEST
-#define RT_CUBOID_PRETEST 0
-#endif
-__device__ __forceinline__ bool cuboid_missed(const double* f, const RayX& r, double t_min, double t_max) {
-  double L = t_min, U = t_max, K = 0.0;
-  bool nan = (t_min != t_min) | (t_max != t_max);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double o = comp(r.o, a), y = comp(r.inv, a);
-    const double ta = (f[a] - o) * y, tb = (f[a + 3] - o) * y;
-    nan |= (ta != ta) | (tb != tb);
-    L = fmax(L, fmin(ta, tb));
-    U = fmin(U, fmax(ta, tb));
-    K = fmax(K, isinf(y) ? 0.0 : fabs(o * y));
-  }
-  const double band = 0x1p-40 * (fabs(L) + fabs(U) + K);
-  const bool ok_band = (band > 0x1p-1000) & (band < INFINITY);
-  return ray_safe(r) & !nan & ((ok_band & (L - U > band)) | (L == INFINITY) | (U == -INFINITY));
-}
-
 // Leaf primitives (Sphere, MovingSphere, Rect{XY,XZ,YZ}, Cuboid): the t of a hit and, for a
 // cuboid, which face (`sub`) won. hit Cuboid (Lib.hs:989-1004) is foldr closerHit over the six
 // faces, each with the full [tmin, tmax]: the later face keeps a tie.
@@ -354,22 +320,7 @@ __device__ __forceinline__ bool prim_t(const Scene& S, const rt_node* n, const R
     return sphere_t(sc, e->f[3], r, t_min, t_max, t);
   }
   if constexpr (!(F & F_RECT)) return false;
-#if RT_CUBOID_TIMING_PROBE
-  // (timing probe only, wrong hits: a plain slab test in place of the six faces — the bound on what a
-  // cheaper exact cuboid test could save)
   if (type == RT_NODE_CUBOID) {
-    double L = t_min, U = t_max;
-    for (int a = 0; a < 3; ++a) {
-      const double ta = (n->f[a] - comp(r.o, a)) * comp(r.inv, a), tb = (n->f[a + 3] - comp(r.o, a)) * comp(r.inv, a);
-      L = fmax(L, fmin(ta, tb));
-      U = fmin(U, fmax(ta, tb));
-    }
-    t = L;
-    return L <= U && L > t_min;
-  }
-#endif
-  if (type == RT_NODE_CUBOID) {
-    if (RT_CUBOID_PRETEST && cuboid_missed(n->f, r, t_min, t_max)) return false;
     bool have = false;
     for (int i = 5; i >= 0; --i) {
       int plane;
@@ -651,7 +602,7 @@ __host__ __device__ constexpr int side_ints_for(int frames) { return 14 + 2 * fr
 constexpr int kSideInts = side_ints_for(RT_MAX_FRAMES);
 // The replacement loop's per-lane LDS ints after the walk stack (philox_loop2's layout, launch_philox's
 // sizing — one definition for both): Side slots for the frame kernels on the binary / mixed walk (loop
-// 1), then, with RT_LANE_LDS (rt_kernels.h), the 4 lane ints (pixel, row, chunk end, depth) of the
+// 1), then, with RT_LANE_LDS, the 4 lane ints (pixel, row, chunk end, depth) of the
 // reference-order kernels (RT_LANE_LDS 1) or of every replacement-loop kernel (2).
 #ifndef RT_LANE_LDS
 #define RT_LANE_LDS 1
@@ -937,18 +888,10 @@ __device__ __forceinline__ void trav_take(const Scene& S, Trav& t, double x, int
 }
 // A hoisted medium's tier-B candidate (RT_BVH_MEDIA_FIRST, rt_bvh.cpp): exactly the walk's medium leaf
 // (trav_leaf: boundary queries over (-inf, inf) and (t1 + eps, inf), the keyed draw, OCML's log), or -1
-// when the ray draws no hit in it (a candidate is >= t_min > 0), or — `bound`, the walk's closest hit when
-// the media are taken after it (RT_MEDIA_AFTER) — when the candidate is certainly beyond `bound`, which
-// trav_take would not take anyway. That is decided without the fp64 log where an fp32 lower bound of the
-// drawn distance already exceeds the room left (below); otherwise the exact expression decides.
-// (measured neutral with the media taken in the prelude, C4 at 100 spp 165.1-166.9 vs 165.4-166.4 ms: off)
-#ifndef RT_LOG_PREFILTER
-#define RT_LOG_PREFILTER 0
-#endif
+// when the ray draws no hit in it (a candidate is >= t_min > 0).
 template <unsigned F>
 __device__ __forceinline__ double hoisted_medium_t(const rt_node* nodes, int id, RayX rx, double t_min, uint32_t k0,
-                                                uint32_t k1, uint32_t walk, uint32_t sample, uint32_t pid,
-                                                double bound = INFINITY) {
+                                                uint32_t k1, uint32_t walk, uint32_t sample, uint32_t pid) {
   Scene S{};
   S.nodes = nodes;
   const rt_node* n = &nodes[id];
@@ -966,56 +909,17 @@ __device__ __forceinline__ double hoisted_medium_t(const rt_node* nodes, int id,
   const double ray_length = vlen(rx.d);
   const double dist_inside = (t2 - rec1t) * ray_length;
   const double rnd = RngPhilox::keyed_at(k0, k1, walk, sample, pid, medium_key(n));
-  // The log skipped where it cannot matter (round 6): hit_dist = |f0| * (-log rnd), f0 = -1/density. With
-  // r32 >= rnd (fp32, rounded up) -log(r32) <= -log(rnd), and OCML's logf is within 2 ulp (2^-22 relative), so
-  // lo = |f0| * (-logf(r32)) * (1 - 2^-20) <= hit_dist. The candidate is used only when hit_dist <= dist_inside
-  // and rec1t + hit_dist / ray_length <= bound; lo beyond both (the second with a relative slack of 2^-30 and
-  // an absolute one of 2^-40 (|rec1t| + |bound|) ray_length, for the roundings of the quotient and the sum)
-  // rejects it exactly as the fp64 expression would. A thin fog's mean free path is far beyond most walks'
-  // closest hits (next_week_final's whole-scene fog: 10 000 units against hits ~100 away), so most draws end
-  // here.
-  if (RT_LOG_PREFILTER) {
-    float r32 = (float)rnd;
-    r32 = (double)r32 < rnd ? __int_as_float(__float_as_int(r32) + 1) : r32;
-    const double lo = fabs(n->f[0]) * (double)(-logf(r32)) * (1.0 - 0x1p-20);
-    const double room = fmin(dist_inside, (bound - rec1t) * ray_length * (1.0 + 0x1p-30) +
-                                              0x1p-40 * (fabs(rec1t) + fabs(bound)) * ray_length);
-    if (lo > room) return -1.0;
-  }
   const double hit_dist = n->f[0] * log_call(rnd);  // (not inlined: log_call)
   if (hit_dist > dist_inside) return -1.0;
   return rec1t + (hit_dist / ray_length);
 }
-// RT_MEDIA_AFTER (round 6, A/B only: measured slower, C4 at 100 spp 158.4 vs 145.4-147.6 ms — without the
-// media's bound the walks visit 10 % more nodes, 33.2 vs 30.1 wide nodes per sample): a world's hoisted
-// media are taken when the walk over the rest of the
-// world has ended (media_after, at the closest hit the walk found) instead of where it starts (the prelude,
-// trav_media_first): the candidate is the same number (the keyed draw names the walk by the stream words
-// consumed, which no walk changes), the closest hit is the least t either way and a medium candidate at exactly
-// a surface's t is flagged as a tie either way (trav_take), but at the end the bound is known, so most draws
-// skip the fp64 log (hoisted_medium_t). The walk then starts below the chain (media_rest).
-#ifndef RT_MEDIA_AFTER
-#define RT_MEDIA_AFTER 0
-#endif
-template <unsigned F>
-__device__ __forceinline__ int media_rest(const Scene& S, int node) {
-  if constexpr ((F & F_MEDIA) != 0 && RT_MEDIA_AFTER) {
-    for (;;) {
-      if (!(node >= 0 && (node & (RT_WNODE | RT_IDTAGS)) == RT_ISBOX)) return node;
-      const rt_node* n = &S.nodes[node & ~(RT_SUB | RT_IDTAGS)];
-      if (!(n->c & RT_BVH_MEDIA_FIRST)) return node;
-      node = n->b | RT_SUB;  // (the rest: below an ordered node, a re-bounded subtree)
-    }
-  }
-  return node;
-}
-// The hoisted media chain from `node` (S.world): each medium's candidate offered to trav_take like a leaf of a
-// re-bounded subtree, without the chain's box tests (they only cull; the medium tests are exact). `after`:
-// the walk over the rest has ended (t.closest is its closest hit, t.node is not touched); else the prelude,
-// which leaves t.node at the rest.
+// The walk's prelude (tier B, worlds with hoisted media): the hoisted media chain at the top of the world
+// (t.node = S.world) taken where lanes start their walks together, each medium's candidate offered to
+// trav_take like a leaf of a re-bounded subtree, without the chain's box tests (they only cull; the medium
+// tests are exact). The walk then starts at the rest (t.node), already bounded by the media.
 template <unsigned F, class R>
-__device__ __forceinline__ void media_chain(const Scene& S, Trav& t, double t_min, Cnt& cnt, const R& g, Side& side,
-                                            int node, bool after) {
+__device__ __forceinline__ void trav_media_first(const Scene& S, Trav& t, double t_min, Cnt& cnt, const R& g,
+                                                 Side& side) {
   if constexpr ((F & F_MEDIA) != 0 && R::kKeyed) {
     // A ray with a NaN in its origin or direction (the segment after a rect hit at t = NaN) hits nothing
     // in the reference: its root box test fails (a NaN slab quotient, Lib.hs:798-814), so it never
@@ -1024,6 +928,7 @@ __device__ __forceinline__ void media_chain(const Scene& S, Trav& t, double t_mi
     // r5; the rest of the walk rejects it, set_ray32).
     const bool dead = (t.ray.o.x != t.ray.o.x) | (t.ray.o.y != t.ray.o.y) | (t.ray.o.z != t.ray.o.z) |
                       (t.ray.d.x != t.ray.d.x) | (t.ray.d.y != t.ray.d.y) | (t.ray.d.z != t.ray.d.z);
+    int node = t.node;
     for (;;) {
       if (!(node >= 0 && (node & (RT_WNODE | RT_IDTAGS)) == RT_ISBOX)) break;
       const rt_node* n = &S.nodes[node & ~(RT_SUB | RT_IDTAGS)];
@@ -1031,28 +936,13 @@ __device__ __forceinline__ void media_chain(const Scene& S, Trav& t, double t_mi
       const int m = n->a & ~RT_IDTAGS;
       if constexpr ((F & F_COUNT) != 0) ++cnt.other;
       // (a NaN closest hit — a rect hit at t = NaN, flagged for a redo — takes no medium: x <= NaN is false)
-      const double x = dead ? -1.0
-                            : hoisted_medium_t<F>(S.nodes, m, t.ray, t_min, g.k0, g.k1, g.consumed(), g.sample, g.pid,
-                                                  after ? t.closest : INFINITY);
+      const double x =
+          dead ? -1.0 : hoisted_medium_t<F>(S.nodes, m, t.ray, t_min, g.k0, g.k1, g.consumed(), g.sample, g.pid);
       if (x >= 0.0 && x <= t.closest) trav_take<F>(S, t, x, m, kSubMedium, side, false, &S.nodes[m], false);
       node = n->b | RT_SUB;
     }
-    if (!after) t.node = node;
+    t.node = node;
   }
-}
-// The walk's prelude (RT_MEDIA_AFTER=0; tier B, worlds with hoisted media): the chain at the top of the world
-// taken where lanes start their walks together, so that the walk starts at the rest already bounded by the
-// media.
-template <unsigned F, class R>
-__device__ __forceinline__ void trav_media_first(const Scene& S, Trav& t, double t_min, Cnt& cnt, const R& g,
-                                                 Side& side) {
-  if constexpr (!RT_MEDIA_AFTER) media_chain<F>(S, t, t_min, cnt, g, side, t.node, false);
-}
-// RT_MEDIA_AFTER: the chain taken at the end of a first walk (not a tie redo, which walks the caller's tree,
-// media included), before the tie check.
-template <unsigned F, class R>
-__device__ __forceinline__ void media_after(const Scene& S, Trav& t, double t_min, Cnt& cnt, const R& g, Side& side) {
-  if constexpr (RT_MEDIA_AFTER) media_chain<F>(S, t, t_min, cnt, g, side, S.world, true);
 }
 // A leaf: a primitive, an instance chain ending in one (its t and face only: the record is built once,
 // in trav_finish), or a ConstantMedium (ref walks only: its one draw happens here, in the reference's
@@ -1064,10 +954,7 @@ __device__ __forceinline__ void media_after(const Scene& S, Trav& t, double t_mi
 template <unsigned F, class R>
 __device__ __forceinline__ void trav_leaf(const Scene& S, Trav& t, const rt_node* n, int id, double t_min, Cnt& cnt,
                                           R& g, Side& side, bool refsem) {
-#ifndef RT_COMPACT_SLEAF
-#define RT_COMPACT_SLEAF 1
-#endif
-  if constexpr ((F & F_QNODE) != 0 || ((F & F_SLEAF) != 0 && RT_COMPACT_SLEAF)) {
+  if constexpr ((F & F_QNODE) != 0) {
     if (id & kSlotTag) {  // a leaf-table slot of a spheres-only world: its (center, radius) quadruple
       if constexpr ((F & F_COUNT) != 0) ++cnt.prim;
       const double2* q = reinterpret_cast<const double2*>(S.sleaves + 4 * (size_t)(id & ~kSlotTag));
@@ -1199,8 +1086,8 @@ __device__ __forceinline__ float4 qplanes(uint32_t q, float s, float o) {
 // One wide node (index `w`): test the four child boxes, enter the nearest accepted child, stack the
 // others (farthest deepest). F_QNODE: the node is read in its quantised form (64 bytes) and its planes
 // decoded; the test over them is the same.
-template <unsigned F = 0, class STK>
-__device__ __forceinline__ bool wide_node(const Scene& S, Trav& t, STK* stk, int stride, int w, bool all = false) {
+template <unsigned F = 0>
+__device__ __forceinline__ bool wide_node(const Scene& S, Trav& t, int* stk, int stride, int w) {
   float4 nx, ny, nz, fx, fy, fz;
   int4 ch;
   if constexpr ((F & F_QNODE) != 0) {
@@ -1242,19 +1129,6 @@ __device__ __forceinline__ bool wide_node(const Scene& S, Trav& t, STK* stk, int
   cswap(k0, c0, k2, c2);
   cswap(k1, c1, k3, c3);
   cswap(k1, c1, k2, c2);
-  if ((F & F_W8) && all) {
-    // (F_W8's farther half: every accepted child stacked, farthest deepest, four slots written — the
-    // stacks have 4 entries of headroom under F_W8)
-    const int a0 = n_hit > 3 ? c3 : (n_hit > 2 ? c2 : (n_hit > 1 ? c1 : c0));
-    const int a1 = n_hit > 3 ? c2 : (n_hit > 2 ? c1 : c0);
-    const int a2 = n_hit > 3 ? c1 : c0;
-    stk[t.sp * stride] = a0;
-    stk[(t.sp + 1) * stride] = a1;
-    stk[(t.sp + 2) * stride] = a2;
-    stk[(t.sp + 3) * stride] = c0;
-    t.sp += n_hit;
-    return n_hit != 0;
-  }
   // Stack the accepted children after c0 without branches, farthest deepest: three slots are always
   // written (slots at or above the new sp are dead; the stacks have 3 entries of headroom for this).
   const int e0 = n_hit > 3 ? c3 : (n_hit > 2 ? c2 : c1);
@@ -1267,54 +1141,20 @@ __device__ __forceinline__ bool wide_node(const Scene& S, Trav& t, STK* stk, int
   return n_hit != 0;
 }
 
-// F_W8 (A/B; measured 1.8x slower on C5: the kernel spills and the 8-wide stack bound costs occupancy,
-// DESIGN.md §0 row 6): node p is the record pair (2p, 2p + 1), its children ordered along the axis in the first
-// record's pad[0] (rt_bvh.cpp build_wide8_bvh). The half farther along the ray on that axis is tested first
-// and every child it accepts stacked; then the nearer half's nearest accepted child is entered and its
-// others stacked above — or, with none, the walk pops (the farther half's nearest, if any).
-template <unsigned F, class STK>
-__device__ __forceinline__ bool wide_node8(const Scene& S, Trav& t, STK* stk, int stride, int p) {
-  const int ax = S.wnodes[2 * p].pad[0];
-  const bool neg = signbit(ax == 0 ? t.i32x : (ax == 1 ? t.i32y : t.i32z));
-  // (one inlined copy of the node test for both halves: a uniform loop)
-  bool in = false;
-#pragma nounroll
-  for (int h = 0; h < 2; ++h) in = wide_node<F>(S, t, stk, stride, 2 * p + ((h == 0) == neg ? 0 : 1), h == 0);
-  return in;
-}
-// Trav::node values of a walk with a postponed leaf (Trav::pend): nothing left but that leaf (kNone); or
-// the next stack entry closes an instance frame, which must wait until the leaf — found inside that frame,
-// in its ray's coordinates — is tested (kHold, the mixed walk).
+// Trav::node of a 4-wide walk with a postponed leaf (Trav::pend) and nothing left but that leaf
 constexpr int kNone = (int)0x80000000;
-constexpr int kHold = (int)0x80000001;
-
-// Leaf postponement in the mixed walk (media / frame worlds over 4-wide trees, F_MIXW; RT_MIXW_POSTPONE=1,
-// A/B only): see walk_until. Measured slower (C4 at 100 spp, same box: 150.5 / 152.7 ms without, 164.4 /
-// 166.1 with; leaf-step thresholds 1 / 8 / 16 of 64: 170-174 / 166 / 188 ms), so off by default.
-#ifndef RT_MIXW_POSTPONE
-#define RT_MIXW_POSTPONE 0
-#endif
-template <unsigned F>
-constexpr bool kMixPostpone = RT_MIXW_POSTPONE && (F & F_MIXW) != 0 && (F & F_WIDE) == 0;
 
 // Pop the next node of a binary (or mixed) walk; false once the walk is over. Frames that close
 // rebuild the parent's ray from the world ray, once for a run of them. (Mixed walks: leaf slots are
-// negative, so only a non-negative entry can be a frame marker.) `hold` (a postponed leaf is waiting,
-// kMixPostpone): a frame marker is not popped — the walk waits at it (kHold) — and an empty stack leaves
-// the walk on (kNone) for its leaf.
-template <unsigned F, class STK>
-__device__ __forceinline__ bool trav_pop_mixed(const Scene& S, Trav& t, const STK* stk, int stride, Side& side,
-                                               double t_min = kEps, bool hold = false) {
+// negative, so only a non-negative entry can be a frame marker.)
+template <unsigned F>
+__device__ __forceinline__ bool trav_pop_mixed(const Scene& S, Trav& t, const int* stk, int stride, Side& side,
+                                               double t_min = kEps) {
   bool reb = false;
   for (;;) {
     const bool end = t.sp == 0;
     const int e = end ? 0 : stk[(--t.sp) * stride];
     const bool frame = (F & F_FRAMES) && ((F & F_MIXW) ? (e >= 0 && (e & RT_FRAME)) : (e & RT_FRAME));
-    if (kMixPostpone<F> && hold && (end || frame)) {  // (reb is false: no frame closes while a leaf waits)
-      t.sp += end ? 0 : 1;
-      t.node = end ? kNone : kHold;
-      return true;
-    }
     if (end || !frame) {
       if ((F & F_FRAMES) && reb) {  // (also at the end: a tie redo walks on from it)
         // the parent's ray, once for the run of closed frames: the world ray rebuilt through the frames
@@ -1337,15 +1177,15 @@ __device__ __forceinline__ bool trav_pop_mixed(const Scene& S, Trav& t, const ST
 // (Translate/Rotate over a BVH, Lib.hs:1029-1052): a tagged stack entry, the frame's id in the
 // lane's Side slots, and the child's ray in Trav::ray; when the entry is popped the parent's ray is
 // rebuilt from the world ray through the frames still open (the same operations as on entry).
-template <unsigned F, class R, class STK>
-__device__ __forceinline__ bool trav_step(const Scene& S, Trav& t, double t_min, STK* stk, int stride, bool joint,
+template <unsigned F, class R>
+__device__ __forceinline__ bool trav_step(const Scene& S, Trav& t, double t_min, int* stk, int stride, bool joint,
                                           Cnt& cnt, R& g, Side& side) {
   bool wide = false;
   if constexpr ((F & F_WIDE) != 0) wide = !t.ref;
   if (wide) {
     if (t.node >= 0) {
       if constexpr ((F & F_COUNT) != 0) ++cnt.wide;
-      if ((F & F_W8) ? wide_node8<F>(S, t, stk, stride, t.node) : wide_node<F>(S, t, stk, stride, t.node)) return true;
+      if (wide_node<F>(S, t, stk, stride, t.node)) return true;
     } else {
       const rt_node* n = &S.leaves[~t.node];
       trav_leaf<F>(S, t, n, ~t.node | kSlotTag, t_min, cnt, g, side, false);
@@ -1457,14 +1297,14 @@ __device__ __forceinline__ bool trav_step(const Scene& S, Trav& t, double t_min,
   } else {
     trav_leaf<F>(S, t, n, id, t_min, cnt, g, side, refsem);
   }
-  if (!to_wide) return trav_pop_mixed<F>(S, t, stk, stride, side, t_min, t.pend >= 0);
+  if (!to_wide) return trav_pop_mixed<F>(S, t, stk, stride, side, t_min);
   }
   if constexpr ((F & F_MIXW) != 0) {  // a 4-wide node (RT_WNODE | index)
     if constexpr ((F & F_COUNT) != 0) ++cnt.wide;
     refresh_ray32(t);
     if (wide_node<F>(S, t, stk, stride, t.node & ~RT_WNODE)) return true;
   }
-  return trav_pop_mixed<F>(S, t, stk, stride, side, kEps, t.pend >= 0);
+  return trav_pop_mixed<F>(S, t, stk, stride, side, kEps);
 }
 
 // ---- the 4-wide walk with postponed leaves (Aila & Laine's while-while, one postponed slot)
@@ -1474,55 +1314,31 @@ __device__ __forceinline__ bool trav_step(const Scene& S, Trav& t, double t_min,
 // step. Culling is looser while a leaf waits (its hit does not yet bound the walk); the closest
 // hit and the tie flag do not depend on the order leaves are tested in (trav_take).
 
-template <class STK>
-__device__ __forceinline__ int trav_pop(Trav& t, const STK* stk, int stride) {
+__device__ __forceinline__ int trav_pop(Trav& t, const int* stk, int stride) {
   return t.sp ? stk[(--t.sp) * stride] : kNone;
 }
-// A second postponed leaf per lane (RT_LEAF_Q=1, round 6, A/B): kept in the lane's LDS word just below its
-// stack (stk[-stride], -1 = empty; the kernels reserve it), filled only while `pend` holds one, so the walk
-// is over exactly when node and pend are. A lane then walks on past its second leaf instead of waiting for
-// the next leaf step. Measured slower (same images): C2 136.0 -> 138.5 ms, C5 at 64 spp 658 -> 670 ms; =2
-// (both leaves tested in one leaf step) 149.5 / 690 ms. Off.
-#ifndef RT_LEAF_Q
-#define RT_LEAF_Q 0
-#endif
-// node -> pend when node is a leaf and the slot is free (else the queue word), then continue with the
-// next stack entry
-template <class STK>
-__device__ __forceinline__ void trav_postpone(Trav& t, STK* stk, int stride) {
-  if (t.node < 0 && t.node != kNone) {
-    if (t.pend < 0) {
-      t.pend = ~t.node;
-      t.node = trav_pop(t, stk, stride);
-    } else if (RT_LEAF_Q && stk[-stride] < 0) {
-      stk[-stride] = (STK)~t.node;
-      t.node = trav_pop(t, stk, stride);
-    }
+// node -> pend when node is a leaf and the slot is free, then continue with the next stack entry
+__device__ __forceinline__ void trav_postpone(Trav& t, int* stk, int stride) {
+  if (t.node < 0 && t.node != kNone && t.pend < 0) {
+    t.pend = ~t.node;
+    t.node = trav_pop(t, stk, stride);
   }
 }
-template <unsigned F, class STK>
-__device__ __forceinline__ void wide_inner(const Scene& S, Trav& t, STK* stk, int stride, Cnt& cnt) {
+template <unsigned F>
+__device__ __forceinline__ void wide_inner(const Scene& S, Trav& t, int* stk, int stride, Cnt& cnt) {
   if constexpr ((F & F_COUNT) != 0) ++cnt.wide;
-  bool in;
-  if constexpr ((F & F_W8) != 0) in = wide_node8<F>(S, t, stk, stride, t.node);
-  else in = wide_node<F>(S, t, stk, stride, t.node);
-  if (!in) t.node = trav_pop(t, stk, stride);
+  if (!wide_node<F>(S, t, stk, stride, t.node)) t.node = trav_pop(t, stk, stride);
   trav_postpone(t, stk, stride);
 }
-template <unsigned F, class R, class STK>
-__device__ __forceinline__ void wide_leaf(const Scene& S, Trav& t, double t_min, STK* stk, int stride, Cnt& cnt, R& g,
+template <unsigned F, class R>
+__device__ __forceinline__ void wide_leaf(const Scene& S, Trav& t, double t_min, int* stk, int stride, Cnt& cnt, R& g,
                                           Side& side) {
-  // (RT_LEAF_Q=2: a lane holding two leaves tests both in one leaf step, one trav_leaf call site)
-#pragma nounroll
-  for (int k = 0; k < (RT_LEAF_Q == 2 ? 2 : 1) && t.pend >= 0; ++k) {
+  // (a loop of at most one trip, not an `if`: as an `if` the 4-wide kernels compile one instruction shorter
+  // and differently scheduled, which has not been measured; this form keeps them as they were timed)
+  for (int k = 0; k < 1 && t.pend >= 0; ++k) {
     const rt_node* n = &S.leaves[t.pend];  // (pend holds the leaf table slot)
     trav_leaf<F>(S, t, n, t.pend | kSlotTag, t_min, cnt, g, side, false);
-    if (RT_LEAF_Q) {
-      t.pend = stk[-stride];
-      stk[-stride] = (STK)-1;
-    } else {
-      t.pend = -1;
-    }
+    t.pend = -1;
   }
   trav_postpone(t, stk, stride);
 }
@@ -1533,70 +1349,10 @@ __device__ __forceinline__ void wide_leaf(const Scene& S, Trav& t, double t_min,
 // wait), so that one step runs the box test alone instead of every node kind its lanes are at
 // (leaf_stop >= the live lanes: every step runs every lane). 4-wide walks: wide-node steps until at
 // most `leaf_stop` walking lanes still look for their first leaf, then one leaf step.
-template <unsigned F, class R, class STK>
-__device__ __forceinline__ void walk_until(const Scene& S, Trav& t, bool& walking, double t_min, STK* stk, int stride,
+template <unsigned F, class R>
+__device__ __forceinline__ void walk_until(const Scene& S, Trav& t, bool& walking, double t_min, int* stk, int stride,
                                            bool joint, int stop, int leaf_stop, Cnt& cnt, R& g, Side& side,
                                            int med_batch = 0) {
-  if constexpr (kMixPostpone<F>) {
-    // The mixed walk with postponed leaves (round 6; the 4-wide walk's scheme, Aila & Laine's while-while
-    // with one slot): a lane that reaches a leaf-table slot of a 4-wide tree (a primitive, a chain, or an
-    // instance frame to open) parks it in `pend` and walks on; the wave runs a leaf step — every lane holding
-    // a leaf tests it (or opens its frame) — once at most leaf_stop of its walking lanes can still step
-    // nodes. So wide / box steps and the leaf kinds' code do not share divergent steps (round 5's profile:
-    // steps mixing wide nodes with leaves and frames were 17 % of C4's steps and 53 % of its time). The
-    // closest hit is the least t over the leaves in any order (tier B: keyed media, re-bounded subtrees;
-    // exact ties are flagged and redone in the reference's order), culling is only looser while a leaf
-    // waits. A waiting leaf is tested in the coordinates it was found in: a lane holding one does not close
-    // an instance frame (kHold), and a parked frame opens in the leaf step above the lane's next node.
-    // Tie redos (t.redo) walk the caller's tree node by node, as before.
-    for (;;) {
-      if (__popcll(__ballot(walking)) <= stop) break;
-      const bool holding = walking && !t.redo && t.pend >= 0 && t.node < 0;  // (at a second leaf, kHold, kNone)
-      const bool seeking = walking && !holding;
-      unsigned kinds = 0;
-      unsigned long long t0 = 0;
-      const bool inner = __popcll(__ballot(seeking)) > leaf_stop || __ballot(holding) == 0;
-      if constexpr ((F & F_COUNT) != 0) {
-        ++(inner ? cnt.islot : cnt.lslot);
-        kinds = inner ? K_WIDE : K_LEAF;
-        t0 = stamp();
-      }
-      // inner step: the seeking lanes' nodes (a lane at a leaf slot only parks it, below); leaf step: the
-      // holding lanes' parked leaves — a leaf's test, or its frame opened — with the lane's next node (a
-      // second leaf slot) put back on the stack, unless the walk waits at a frame marker (kHold) or is done
-      // (kNone). One trav_step call site for both (a second inlined copy cost registers).
-      bool go;
-      if (inner) {
-        go = seeking && (t.redo || t.node >= 0);
-      } else {
-        go = holding;
-        if (holding) {
-          const int saved = t.node;
-          if (saved != kNone && saved != kHold) stk[(t.sp++) * stride] = saved;
-          t.node = ~t.pend;
-          t.pend = -1;
-        }
-      }
-      if (go) walking = trav_step<F>(S, t, t_min, stk, stride, joint, cnt, g, side) || t.pend >= 0;
-      // a leaf slot reached (by this step, or waiting since the last) with the slot free: park it, walk on
-      if (walking && !t.redo && t.pend < 0 && t.node < 0 && t.node != kNone && t.node != kHold) {
-        t.pend = ~t.node;
-        // (trav_pop_mixed with `hold`: the next entry, or wait at a frame marker, or nothing left)
-        const int e = t.sp ? stk[(t.sp - 1) * stride] : 0;
-        const bool fr = e >= 0 && (e & RT_FRAME);
-        t.node = t.sp == 0 ? kNone : (fr ? kHold : e);
-        t.sp -= (t.sp == 0 || fr) ? 0 : 1;
-      }
-      if constexpr ((F & F_COUNT) != 0) {
-        const unsigned long long t1 = stamp();
-        if (cnt.prof && __lane_id() == (unsigned)(__ffsll((long long)__ballot(true)) - 1)) {
-          atomicAdd(&cnt.prof[kinds], t1 - t0);
-          atomicAdd(&cnt.prof[32 + kinds], 1ull);
-        }
-      }
-    }
-    return;
-  }
   if constexpr ((F & F_WIDE) == 0) {
     for (;;) {
       const int n_walk = __popcll(__ballot(walking));
@@ -1627,16 +1383,7 @@ __device__ __forceinline__ void walk_until(const Scene& S, Trav& t, bool& walkin
           // or nothing else walks, so that fewer steps carry the medium code
           const bool at_med = walking && t.node >= 0 && (t.node & (RT_WNODE | RT_IDTAGS)) == RT_ISMED;
           const int n_med = __popcll(__ballot(at_med));
-          if constexpr (RT_FRAME_BATCH && (F & F_MIXW) && (F & F_FRAMES)) {
-            // (likewise lanes at an instance frame found by a 4-wide node: its leaf slot lacks bit 26)
-            const bool at_frm = walking && t.node < 0 && !(t.node & RT_ISMED);
-            const int n_frm = __popcll(__ballot(at_frm));
-            const bool hold = (n_med < med_batch && at_med) || (n_frm < med_batch && at_frm);
-            go = walking && !hold;
-            if (__ballot(go) == 0) go = walking;  // (every walking lane held: all go)
-          } else {
-            if (n_med < med_batch && n_med < n_walk) go = walking && !at_med;
-          }
+          if (n_med < med_batch && n_med < n_walk) go = walking && !at_med;
         }
       }
       if constexpr ((F & F_COUNT) != 0) {  // counting build: wave steps, and the node kinds each one runs
