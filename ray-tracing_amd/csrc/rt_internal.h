@@ -58,6 +58,14 @@ inline int bvh_stack_need(const rt_node& x, int need_a, int need_b) {
 
 }  // namespace rt
 
+// The work geometry a tier-B launch puts into its launch constants (rt_kernels.h LaunchConst), checked
+// without a device: for shard p->shard_rank and a launch of `n_chunks` sample chunks from `chunk_first`
+// whose last `tail_items` work-items are dealt one sample per unit, the device's decomposition (work_unit)
+// of the units [first, first + n): out5[i] = {valid, px, row, s0, s1}, out_slot[i] the chunk sum's slot
+// (kTailSlot + unit for a tail unit); out_totals = {work_total, items_total, tail_start, slab, chunk}.
+extern "C" int rt_internal_work_units(const rt_render_params* p, int chunk_first, int n_chunks, long long tail_items,
+                                      uint32_t first, int n, int32_t* out5, int64_t* out_slot, int64_t* out_totals);
+
 struct rt_builder {
   uint64_t seed, gamma;  // RandGen (SMGen)
   std::vector<rt_node> nodes;

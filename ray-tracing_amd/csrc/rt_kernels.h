@@ -36,12 +36,22 @@ inline UDiv make_udiv(uint32_t d) {
   const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
   return UDiv{(uint32_t)m, l < 1 ? l : 1, l > 1 ? l - 1 : 0};
 }
-__device__ __forceinline__ uint32_t udiv(uint32_t n, UDiv d) {
+__host__ __device__ __forceinline__ uint32_t udiv(uint32_t n, UDiv d) {
+#ifdef __HIP_DEVICE_COMPILE__
   const uint32_t t = __umulhi(d.m, n);
+#else  // (the host evaluates the work decomposition for the launch-geometry check)
+  const uint32_t t = (uint32_t)(((uint64_t)d.m * n) >> 32);
+#endif
   return (t + ((n - t) >> d.s1)) >> d.s2;
 }
 
-struct RenderArgs {
+// The launch's constants: everything a launch passes to its kernels. The small kernels (combine_chunks,
+// tail_combine, frame_resolve) and tier A take it by value. The tier-B render kernels get a device copy
+// (RenderArgs::lc, written by launch_setup ahead of the launch) and stage it in LDS once per workgroup:
+// the persistent loops read the camera, the table pointers, the work geometry and the claim parameters
+// from there where they use them, instead of holding them in scalar registers (and their spill lanes)
+// across the walk. DESIGN.md §3.1.
+struct LaunchConst {
   Scene S;
   rt_camera cam;
   int W, H, spp, max_depth;
@@ -85,10 +95,41 @@ struct RenderArgs {
   double* tail_buf;      // [unit][3]
   UDiv div_chunk;        // by chunk
 };
+// (its LDS copy sits at the start of the workgroup's lane-stack memory, 16-byte aligned)
+constexpr int kLcBytes = (int)((sizeof(LaunchConst) + 15) & ~(size_t)15);
+
+// Kernel arguments of the tier-B render kernels: what a walk step touches, and the launch constants'
+// device copy. Of S the walks read the node tables, `world`, `ref_walk` and `frames`; shading reads the
+// scene through the LDS copy.
+struct RenderArgs {
+  Scene S;
+  const LaunchConst* lc;
+  uint64_t seed;  // (scalar: the Philox round keys are derived from it where a block is computed)
+  uint32_t flags;
+  int trav_stop, leaf_stop, box_first, med_batch;  // (as in LaunchConst)
+  unsigned long long* prof;
+};
+
+// Copies the launch constants to `lds` (kLcBytes, 16-byte aligned); the caller's barrier publishes them.
+__device__ __forceinline__ const LaunchConst& stage_const(const RenderArgs& A, void* lds) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(A.lc);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(lds);
+  for (int i = threadIdx.x; i < (int)(sizeof(LaunchConst) / 4); i += blockDim.x) dst[i] = src[i];
+  return *reinterpret_cast<const LaunchConst*>(lds);
+}
+
+// Writes a launch's constants to their device copy and resets the work counter (one block, ahead of
+// the render kernel on its stream; the struct travels as a kernel argument, copied at launch).
+__global__ void __launch_bounds__(64) launch_setup(LaunchConst L, LaunchConst* dst) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&L);
+  uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+  for (int i = threadIdx.x; i < (int)(sizeof(LaunchConst) / 4); i += 64) d[i] = src[i];
+  if (threadIdx.x == 0) *L.counter = 0ull;
+}
 
 // Slab pixel index -> image pixel (tile-major, 8x8 blocks inside a tile). Slab indices are < 2^32
 // (launch_philox checks).
-__device__ __forceinline__ bool work_pixel(const RenderArgs& A, uint32_t w, int& px, int& row) {
+__host__ __device__ __forceinline__ bool work_pixel(const LaunchConst& A, uint32_t w, int& px, int& row) {
   const uint32_t tp = (uint32_t)(A.tile * A.tile);
   const uint32_t lt = udiv(w, A.div_tp);
   const uint32_t within = w - lt * tp;
@@ -106,8 +147,8 @@ __device__ __forceinline__ bool work_pixel(const RenderArgs& A, uint32_t w, int&
 // tile, so a wave's 64 consecutive items are one 8x8 pixel block at one chunk (coherent rays).
 // Returns false for pixels outside the image; else the sample range [s0, s1) and the chunk
 // sum's slot in `partial`.
-__device__ __forceinline__ bool work_item(const RenderArgs& A, uint32_t wi, int& px, int& row, int& s0, int& s1,
-                                          long long& slot) {
+__host__ __device__ __forceinline__ bool work_item(const LaunchConst& A, uint32_t wi, int& px, int& row, int& s0,
+                                                   int& s1, long long& slot) {
   const uint32_t tp = (uint32_t)(A.tile * A.tile);
   const uint32_t lw = udiv(wi, A.div_tile);  // by tp * chunks
   const uint32_t rem = wi - lw * tp * (uint32_t)A.chunks;
@@ -116,7 +157,7 @@ __device__ __forceinline__ bool work_item(const RenderArgs& A, uint32_t wi, int&
   const uint32_t idx = lt * tp + (rem - k * tp);
   if (!work_pixel(A, idx, px, row)) return false;
   s0 = (A.chunk_base + (int)k) * A.chunk;
-  s1 = min(A.spp, s0 + A.chunk);
+  s1 = A.spp < s0 + A.chunk ? A.spp : s0 + A.chunk;
   slot = (long long)k * A.slab + idx;
   return s0 < s1;
 }
@@ -126,7 +167,7 @@ __device__ __forceinline__ void store_partial_at(double* base, long long slot, V
   q[1] = sum.y;
   q[2] = sum.z;
 }
-__device__ __forceinline__ void store_partial(const RenderArgs& A, long long slot, V3 sum) {
+__device__ __forceinline__ void store_partial(const LaunchConst& A, long long slot, V3 sum) {
   store_partial_at(A.partial, slot, sum);
 }
 // Sample-granular tails: in the full variants' kernels only (media / frame worlds, C4), whose work-items
@@ -139,8 +180,8 @@ constexpr bool kTail = (F & F_FRAMES) != 0;
 // kTailSlot + its index (its colour goes to tail_buf); false for pixels outside the image and for units
 // past the work-item's last sample.
 constexpr long long kTailSlot = 1ll << 40;
-__device__ __forceinline__ bool work_unit(const RenderArgs& A, uint32_t wi, int& px, int& row, int& s0, int& s1,
-                                          long long& slot) {
+__host__ __device__ __forceinline__ bool work_unit(const LaunchConst& A, uint32_t wi, int& px, int& row, int& s0,
+                                                   int& s1, long long& slot) {
   if ((long long)wi < A.tail_start) return work_item(A, wi, px, row, s0, s1, slot);
   const uint32_t u = wi - (uint32_t)A.tail_start;
   const uint32_t q = udiv(u, A.div_chunk);
@@ -180,7 +221,7 @@ __device__ __forceinline__ V3 nan_zero(V3 a) {
   return v3(a.x != a.x ? 0.0 : a.x, a.y != a.y ? 0.0 : a.y, a.z != a.z ? 0.0 : a.z);
 }
 
-__device__ __forceinline__ void store_pixel(const RenderArgs& A, long long idx, V3 avg) {
+__device__ __forceinline__ void store_pixel(const LaunchConst& A, long long idx, V3 avg) {
   A.out_rgb[idx * 3 + 0] = scale_color(avg.x);
   A.out_rgb[idx * 3 + 1] = scale_color(avg.y);
   A.out_rgb[idx * 3 + 2] = scale_color(avg.z);
@@ -224,9 +265,10 @@ __device__ __forceinline__ bool shade_hit(const Scene& S, bool got, const Hit& h
 
 // One path segment: closest hit, then emission/background or a scatter. Returns true when the
 // path ends, with its contribution in `contrib` (rayColor, Lib.hs:1298-1333).
-template <unsigned F, class R>
-__device__ __forceinline__ bool segment(const RenderArgs& A, const Scene& S, Ray& ray, V3& thr, int& depth, R& g,
-                                        int* stk, V3& contrib, Cnt& cnt, int stride = RT_BLOCK,
+// (S: the walk's scene, its node tables possibly in LDS; SC: the scene shading reads)
+template <unsigned F, class R, class AT>
+__device__ __forceinline__ bool segment(const AT& A, const Scene& S, const Scene& SC, Ray& ray, V3& thr, int& depth,
+                                        R& g, int* stk, V3& contrib, Cnt& cnt, int stride = RT_BLOCK,
                                         unsigned long long* t_trav = nullptr) {
   if (depth <= 0) {  // d <= 0 -> black
     contrib = vmul(thr, v3(0.0, 0.0, 0.0));
@@ -237,7 +279,7 @@ __device__ __forceinline__ bool segment(const RenderArgs& A, const Scene& S, Ray
   const bool got = traverse<F>(S, S.ref_walk ? S.world_ref : S.world, ray, kEps, INFINITY, h, g, stk,
                                !(A.flags & RT_FLAG_REFERENCE_CULL), cnt, stride);
   if constexpr ((F & F_COUNT) != 0) *t_trav = stamp();
-  return shade_hit<F>(S, got, h, ray, thr, depth, g, contrib, cnt);
+  return shade_hit<F>(SC, got, h, ray, thr, depth, g, contrib, cnt);
 }
 
 // ---------------------------------------------------------------- tier B: Philox per (pixel, sample)
@@ -249,7 +291,8 @@ __device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long 
 
 // The persistent tier-B loop, shared by the global-memory and LDS-staged kernels.
 template <unsigned F>
-__device__ __forceinline__ void philox_loop(const RenderArgs& A, const Scene& S, int* stk, int stride) {
+__device__ __forceinline__ void philox_loop(const RenderArgs& A, const LaunchConst& L, const Scene& S, int* stk,
+                                            int stride) {
   const int lane = threadIdx.x & 63;
   const unsigned long long lanes_below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 
@@ -273,13 +316,13 @@ __device__ __forceinline__ void philox_loop(const RenderArgs& A, const Scene& S,
       if (!mask) break;
       const int leader = __ffsll((long long)mask) - 1;
       unsigned long long base = 0;
-      if (lane == leader) base = atomicAdd(A.counter, (unsigned long long)__popcll(mask));
+      if (lane == leader) base = atomicAdd(L.counter, (unsigned long long)__popcll(mask));
       base = __shfl(base, leader);
       if (need) {
         const long long wi = (long long)(base + __popcll(mask & lanes_below));
-        if (wi >= A.work_total) {
+        if (wi >= L.work_total) {
           done = true;
-        } else if (work_item(A, (uint32_t)wi, px, row, s, s_end, w)) {
+        } else if (work_item(L, (uint32_t)wi, px, row, s, s_end, w)) {
           sum = v3(0, 0, 0);
           path = false;
         } else {
@@ -289,16 +332,16 @@ __device__ __forceinline__ void philox_loop(const RenderArgs& A, const Scene& S,
     }
     if (w < 0) break;  // no pixel left for this lane (done); the others keep going
     if (!path) {  // start sample s: uniformRandomUVs' pair, then getRay
-      const uint32_t pid = (uint32_t)((long long)row * A.W + px);
+      const uint32_t pid = (uint32_t)((long long)row * L.W + px);
       g.init(A.seed, pid, (uint32_t)s);
       g.reserve(3);  // the UV pair and the first disk try
       const double ru = g.draw(), rv = g.draw();
-      const int y = A.H - 1 - row;
-      const double u = ((double)px + ru) / (double)A.W;
-      const double v = ((double)y + rv) / (double)A.H;
-      ray = get_ray(A.cam, u, v, g);
+      const int y = L.H - 1 - row;
+      const double u = ((double)px + ru) / (double)L.W;
+      const double v = ((double)y + rv) / (double)L.H;
+      ray = get_ray(L.cam, u, v, g);
       thr = v3(1.0, 1.0, 1.0);
-      depth = A.max_depth;
+      depth = L.max_depth;
       path = true;
     }
     V3 contrib;
@@ -307,7 +350,7 @@ __device__ __forceinline__ void philox_loop(const RenderArgs& A, const Scene& S,
       s1 = stamp();
       s2 = s1;
     }
-    const bool ended = segment<F>(A, S, ray, thr, depth, g, stk, contrib, cnt, stride, &s2);
+    const bool ended = segment<F>(A, S, L.S, ray, thr, depth, g, stk, contrib, cnt, stride, &s2);
     if constexpr ((F & F_COUNT) != 0) {
       const unsigned long long s3 = stamp();
       ph_acq += s1 - s0;
@@ -325,31 +368,35 @@ __device__ __forceinline__ void philox_loop(const RenderArgs& A, const Scene& S,
       ++s;
       const bool all_nan = (A.flags & RT_FLAG_NAN_CULL) && sum.x != sum.x && sum.y != sum.y && sum.z != sum.z;
       if (s == s_end || all_nan) {
-        store_partial(A, w, sum);
+        store_partial(L, w, sum);
         w = -1;
       }
     }
   }
   if constexpr ((F & F_COUNT) != 0) {  // lanes re-converge after the loop: one add per wave
-    wave_add(&A.work[0], segs);
-    wave_add(&A.work[1], cnt.box);
-    wave_add(&A.work[2], cnt.prim);
-    wave_add(&A.work[3], cnt.other);
-    wave_add(&A.work[4], cnt.light);
-    wave_add(&A.work[5], blocks);
-    wave_add(&A.work[6], samples);
+    wave_add(&L.work[0], segs);
+    wave_add(&L.work[1], cnt.box);
+    wave_add(&L.work[2], cnt.prim);
+    wave_add(&L.work[3], cnt.other);
+    wave_add(&L.work[4], cnt.light);
+    wave_add(&L.work[5], blocks);
+    wave_add(&L.work[6], samples);
     if ((threadIdx.x & 63) == 0) {  // wave-uniform phase times (s_memtime ticks)
-      atomicAdd(&A.work[8], ph_acq);
-      atomicAdd(&A.work[9], ph_trav);
-      atomicAdd(&A.work[10], ph_shade);
+      atomicAdd(&L.work[8], ph_acq);
+      atomicAdd(&L.work[9], ph_trav);
+      atomicAdd(&L.work[10], ph_shade);
     }
   }
 }
 
 template <unsigned F, int WAVES>
 __global__ void __launch_bounds__(RT_BLOCK, WAVES) render_philox(RenderArgs A) {
-  __shared__ int stk_mem[RT_STACK * RT_BLOCK];
-  philox_loop<F>(A, A.S, &stk_mem[threadIdx.x], RT_BLOCK);
+  // (the launch constants ahead of the stacks, in one array: stack stores may alias them, so their reads
+  // stay where the loop uses them)
+  __shared__ __attribute__((aligned(16))) int stk_mem[kLcBytes / 4 + RT_STACK * RT_BLOCK];
+  const LaunchConst& L = stage_const(A, stk_mem);
+  __syncthreads();
+  philox_loop<F>(A, L, A.S, &stk_mem[kLcBytes / 4 + threadIdx.x], RT_BLOCK);
 }
 
 // LDS-staged variant: one workgroup of WAVES*4 waves per CU; the whole node array is copied
@@ -358,19 +405,21 @@ __global__ void __launch_bounds__(RT_BLOCK, WAVES) render_philox(RenderArgs A) {
 template <unsigned F, int WAVES>
 __global__ void __launch_bounds__(WAVES * 256, WAVES) render_philox_lds(RenderArgs A, int n_nodes, int stack_entries) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  rt_node* nodes = reinterpret_cast<rt_node*>(lds);
+  // (the launch constants first, kLcBytes, then the nodes, then the stacks)
+  const LaunchConst& L = stage_const(A, lds);
+  rt_node* nodes = reinterpret_cast<rt_node*>(lds + kLcBytes);
   {
     const uint4* src = reinterpret_cast<const uint4*>(A.S.nodes);
-    uint4* dst = reinterpret_cast<uint4*>(lds);
+    uint4* dst = reinterpret_cast<uint4*>(lds + kLcBytes);
     const int n16 = n_nodes * (int)(sizeof(rt_node) / 16);
     for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
   }
   __syncthreads();
   Scene S = A.S;
   S.nodes = nodes;
-  int* stk = reinterpret_cast<int*>(lds + (size_t)n_nodes * sizeof(rt_node)) + threadIdx.x;
+  int* stk = reinterpret_cast<int*>(lds + kLcBytes + (size_t)n_nodes * sizeof(rt_node)) + threadIdx.x;
   (void)stack_entries;
-  philox_loop<F>(A, S, stk, WAVES * 256);
+  philox_loop<F>(A, L, S, stk, WAVES * 256);
 }
 
 
@@ -380,8 +429,8 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES) render_philox_lds(RenderAr
 // node at a time until at most trav_stop/64 of the live lanes are still walking. Lanes never
 // wait for the slowest walk of their wave, and shading runs for many lanes at once.
 template <unsigned F>
-__device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S, int* stk, int stride, int* side_p,
-                                             volatile uint32_t* wq) {
+__device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchConst& L, const Scene& S, int* stk,
+                                             int stride, int* side_p, volatile uint32_t* wq) {
   const int lane = threadIdx.x & 63;
   const unsigned long long lanes_below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
@@ -430,8 +479,8 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
     const bool all_nan = (A.flags & RT_FLAG_NAN_CULL) && sm.x != sm.x && sm.y != sm.y && sm.z != sm.z;
     if (s == s_end || all_nan) {
       // (a tail unit: its one sample's colour, summed in order with its chunk's others by tail_combine)
-      if (kTail<F> && w >= kTailSlot) store_partial_at(A.tail_buf, w - kTailSlot, contrib);
-      else store_partial(A, w, sm);
+      if (kTail<F> && w >= kTailSlot) store_partial_at(L.tail_buf, w - kTailSlot, contrib);
+      else store_partial(L, w, sm);
       w = -1;
     }
   };
@@ -454,7 +503,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
     if (ready && (t.tie || (kRefMixed<F> && t.lite)) && !t.redo && !all_nan3(thr)) {
       ready = false;
       if constexpr ((F & F_COUNT) != 0) ++cnt.ties;
-      trav_redo<F>(t, S.world_ref, INFINITY);
+      trav_redo<F>(t, L.S.world_ref, INFINITY);
       // (the redo's binary box tests need 1/d: recomputed here, the same values, so that the 4-wide
       // walk need not carry Trav::ray.inv)
       if constexpr ((F & F_WIDE) != 0) t.ray = prep(plain(t.ray));
@@ -468,10 +517,10 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
       ready = false;
       Hit h;
       Ray ray = plain(t.ray);  // (every frame has closed: the world ray again)
-      const bool got = trav_finish<F>(S, t, ray, kEps, h, side);
+      const bool got = trav_finish<F>(L.S, t, ray, kEps, h, side);
       V3 contrib;
       V3 th = thr;
-      if (shade_hit<F>(S, got, h, ray, th, depth, g, contrib, cnt)) {
+      if (shade_hit<F>(L.S, got, h, ray, th, depth, g, contrib, cnt)) {
         end_sample(contrib);
       } else if (depth <= 0) {  // rayColor's d <= 0 -> black (thr * 0 keeps a NaN throughput NaN)
         end_sample(vmul(th, v3(0.0, 0.0, 0.0)));
@@ -488,7 +537,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
     if constexpr ((F & F_COUNT) != 0) s0b = stamp();
     while (!walking && !start) {
       // acquire work-items for idle lanes: from the wave's claimed range first; when it runs short,
-      // one atomic claims a batch of A.batch more (exactly the lanes' need once the counter is near
+      // one atomic claims a batch of L.batch more (exactly the lanes' need once the counter is near
       // the end, so that no wave hoards the frame's last items)
       for (;;) {
         const bool need = (w < 0) && !done;
@@ -502,14 +551,14 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
           const int leader = __ffsll((long long)mask) - 1;
           unsigned long long claim = 0;
           if (lane == leader) {
-            // batch: A.batch items, fewer as the frame runs out (the wave's last claim end tells it
+            // batch: L.batch items, fewer as the frame runs out (the wave's last claim end tells it
             // roughly how many remain), so that no wave hoards the tail; never less than the need
             const uint32_t want = n_need - avail;
-            const long long rem = A.work_total - (long long)q_end;
-            const uint32_t b = rem <= 0 ? 0u : max((uint32_t)A.batch_floor,
-                                                   (uint32_t)fminf((float)A.batch, (float)rem * A.batch_per_item));
+            const long long rem = L.work_total - (long long)q_end;
+            const uint32_t b = rem <= 0 ? 0u : max((uint32_t)L.batch_floor,
+                                                   (uint32_t)fminf((float)L.batch, (float)rem * L.batch_per_item));
             const uint32_t got = want < b ? b : want;
-            const unsigned long long c0 = atomicAdd(A.counter, (unsigned long long)got);
+            const unsigned long long c0 = atomicAdd(L.counter, (unsigned long long)got);
             // (claims past 2^32 only happen once every item is handed out: clamp, the lanes see
             // `done`); the claim and its size travel together in one broadcast
             claim = (c0 < 0xffff0000ull ? c0 : 0xffff0000ull) | ((unsigned long long)got << 32);
@@ -521,10 +570,10 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
         const uint32_t rank = (uint32_t)__popcll(mask & lanes_below);
         if (need) {
           const long long wi = (long long)(rank < avail ? q_next + rank : base2 + (rank - avail));
-          if (wi >= A.work_total) {
+          if (wi >= L.work_total) {
             done = true;
-          } else if (kTail<F> ? work_unit(A, (uint32_t)wi, px, row, s, s_end, w)
-                              : work_item(A, (uint32_t)wi, px, row, s, s_end, w)) {
+          } else if (kTail<F> ? work_unit(L, (uint32_t)wi, px, row, s, s_end, w)
+                              : work_item(L, (uint32_t)wi, px, row, s, s_end, w)) {
             sum = v3(0, 0, 0);
           } else {
             w = -1;
@@ -538,19 +587,19 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
       }
       if (w < 0) break;  // no work left for this lane
       // start sample s: uniformRandomUVs' pair, then getRay
-      const uint32_t pid = (uint32_t)((long long)row * A.W + px);
+      const uint32_t pid = (uint32_t)((long long)row * L.W + px);
       g.init(A.seed, pid, (uint32_t)s);
       g.reserve(3);  // the UV pair and the first disk try
       const double ru = g.draw(), rv = g.draw();
-      const int y = A.H - 1 - row;
-      const double u = ((double)px + ru) / (double)A.W;
-      const double v = ((double)y + rv) / (double)A.H;
-      const Ray cray = get_ray(A.cam, u, v, g);
+      const int y = L.H - 1 - row;
+      const double u = ((double)px + ru) / (double)L.W;
+      const double v = ((double)y + rv) / (double)L.H;
+      const Ray cray = get_ray(L.cam, u, v, g);
       t.ray.o = cray.o;
       t.ray.d = cray.d;
       t.ray.tm = cray.tm;
       thr = v3(1.0, 1.0, 1.0);
-      depth = A.max_depth;
+      depth = L.max_depth;
       if (depth <= 0) {
         end_sample(vmul(v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0)));
         continue;
@@ -582,23 +631,23 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const Scene& S
     }
   }
   if constexpr ((F & F_COUNT) != 0) {
-    wave_add(&A.work[0], segs);
-    wave_add(&A.work[1], cnt.box);
-    wave_add(&A.work[2], cnt.prim);
-    wave_add(&A.work[3], cnt.other);
-    wave_add(&A.work[4], cnt.light);
-    wave_add(&A.work[5], blocks);
-    wave_add(&A.work[6], samples);
-    wave_add(&A.work[7], cnt.wide);
-    wave_add(&A.work[11], cnt.islot);
-    wave_add(&A.work[12], cnt.lslot);
-    wave_add(&A.work[13], cnt.oslot);
-    wave_add(&A.work[14], cnt.phit);
-    wave_add(&A.work[15], cnt.ties);
+    wave_add(&L.work[0], segs);
+    wave_add(&L.work[1], cnt.box);
+    wave_add(&L.work[2], cnt.prim);
+    wave_add(&L.work[3], cnt.other);
+    wave_add(&L.work[4], cnt.light);
+    wave_add(&L.work[5], blocks);
+    wave_add(&L.work[6], samples);
+    wave_add(&L.work[7], cnt.wide);
+    wave_add(&L.work[11], cnt.islot);
+    wave_add(&L.work[12], cnt.lslot);
+    wave_add(&L.work[13], cnt.oslot);
+    wave_add(&L.work[14], cnt.phit);
+    wave_add(&L.work[15], cnt.ties);
     if ((threadIdx.x & 63) == 0) {
-      atomicAdd(&A.work[8], ph_setup);
-      atomicAdd(&A.work[9], ph_trav);
-      atomicAdd(&A.work[10], ph_shade);
+      atomicAdd(&L.work[8], ph_setup);
+      atomicAdd(&L.work[9], ph_trav);
+      atomicAdd(&L.work[10], ph_shade);
     }
   }
 }
@@ -615,9 +664,12 @@ constexpr int lane_ints() {
 // per SIMD).
 template <unsigned F, int WAVES>
 __global__ void __launch_bounds__(RT_BLOCK, WAVES) render_philox2(RenderArgs A, int stack_entries) {
-  extern __shared__ __attribute__((aligned(16))) int stk_mem[];
+  extern __shared__ __attribute__((aligned(16))) int stk_mem[];  // (the launch constants, kLcBytes, first)
   __shared__ uint32_t wave_q[RT_BLOCK / 64][2];
-  philox_loop2<F>(A, A.S, &stk_mem[threadIdx.x], RT_BLOCK, &stk_mem[stack_entries * RT_BLOCK + threadIdx.x],
+  const LaunchConst& L = stage_const(A, stk_mem);
+  __syncthreads();
+  int* lane0 = &stk_mem[kLcBytes / 4 + threadIdx.x];
+  philox_loop2<F>(A, L, A.S, lane0, RT_BLOCK, lane0 + stack_entries * RT_BLOCK,
                   wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
 }
 
@@ -630,10 +682,13 @@ __global__ void __launch_bounds__(RT_BLOCK, WAVES) render_philox2(RenderArgs A, 
 template <unsigned F, int WAVES, bool LEAF_LDS = false>
 __global__ void __launch_bounds__(WAVES * 256, WAVES)
     render_philox2_lds(RenderArgs A, int n_nodes, int stack_entries, int n_leaves) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds0[];
   __shared__ uint32_t wave_q[WAVES * 4][2];  // (static: kStaticLds bytes ahead of the dynamic LDS)
   constexpr int rec = (F & F_WIDE) ? (int)sizeof(rt_wnode) : (int)sizeof(rt_node);
   constexpr int lrec = (int)sizeof(rt_node);
+  // (dynamic LDS: the launch constants, kLcBytes, then the nodes, the leaf table, the lanes' stacks and slots)
+  const LaunchConst& L = stage_const(A, lds0);
+  unsigned char* lds = lds0 + kLcBytes;
   {
     const uint4* src = (F & F_WIDE) ? reinterpret_cast<const uint4*>(A.S.wnodes)
                                     : reinterpret_cast<const uint4*>(A.S.nodes);
@@ -658,12 +713,12 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES)
   // (per lane: stack_entries stack entries, then side_ints_of Side slots, then lane_lds_of's 4 lane ints —
   // launch_philox sizes the dynamic LDS with the same helpers)
   int* side_p = reinterpret_cast<int*>(lane_base + (size_t)stack_entries * lanes * sizeof(int)) + threadIdx.x;
-  philox_loop2<F>(A, S, stk, lanes, side_p, wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
+  philox_loop2<F>(A, L, S, stk, lanes, side_p, wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
 }
 
 // The tail's work-items (work_unit): each chunk's sample colours added in sample order from 0, as the
 // lane that renders a whole chunk adds them (end_sample), into the chunk's slot.
-__global__ void __launch_bounds__(256) tail_combine(RenderArgs A) {
+__global__ void __launch_bounds__(256) tail_combine(LaunchConst A) {
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= A.items_total - A.tail_start) return;
   int px, row, s0, s1;
@@ -677,7 +732,7 @@ __global__ void __launch_bounds__(256) tail_combine(RenderArgs A) {
 
 // Tier B: a slab pixel's chunk sums added in chunk order, then averaged and stored (rt.h); with chunk
 // batches, each batch's chunks are added to the running sum of the batches before it.
-__global__ void __launch_bounds__(256) combine_chunks(RenderArgs A) {
+__global__ void __launch_bounds__(256) combine_chunks(LaunchConst A) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= A.slab) return;
   int px, row;
@@ -710,7 +765,7 @@ constexpr int kExactColsPerWave = RT_EXACT_COLS_PER_WAVE;
 // dependent node read's latency is the lane's own time: from L2 it cost the Cornell box ~10x the
 // 16-thread CPU oracle's time.
 template <unsigned F, bool LDS = false>
-__global__ void __launch_bounds__(RT_BLOCK) render_exact(RenderArgs A, int n_nodes) {
+__global__ void __launch_bounds__(RT_BLOCK) render_exact(LaunchConst A, int n_nodes) {
   __shared__ int stk_mem[RT_STACK * RT_BLOCK];
   int* stk = &stk_mem[threadIdx.x];
   // Tier A reproduces the reference's stream exactly, exact ties included: walk the caller's tree.
@@ -751,7 +806,7 @@ __global__ void __launch_bounds__(RT_BLOCK) render_exact(RenderArgs A, int n_nod
       int depth = A.max_depth;
       Cnt cnt{};
       for (int seg = 0;; ++seg) {
-        const bool end = segment<F>(A, S, ray, thr, depth, g, stk, contrib, cnt);
+        const bool end = segment<F>(A, S, S, ray, thr, depth, g, stk, contrib, cnt);
         if (traced && tn < A.trace_cap) {  // (rt_debug_exact_trace: the oracle's oracle_exact_trace layout)
           double* o = A.trace + 10 * (long long)tn++;
           o[0] = row, o[1] = j, o[2] = end ? -(seg + 1) : seg;
@@ -804,7 +859,7 @@ __device__ __forceinline__ long long frame_slot(long long i, int W, int tile, in
 // counts[0] += pixels whose sum has a NaN channel, counts[1] += bytes that change. One pass; the counts
 // are reduced over each wave with ballots, over the block's 4 waves through LDS, and leave the block as
 // one atomic per counter.
-__global__ void __launch_bounds__(256) frame_resolve(RenderArgs A, int samples, unsigned long long* counts) {
+__global__ void __launch_bounds__(256) frame_resolve(LaunchConst A, int samples, unsigned long long* counts) {
   __shared__ unsigned wave_nan[4], wave_chg[4];
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   bool nan = false, c0 = false, c1 = false, c2 = false;

@@ -15,6 +15,9 @@
 //  * forward throughput (thr *= att * (spdf / pdf)) instead of the reference's continuation;
 //    colour never feeds control flow or the RNG, so this changes rounding only;
 //  * traversal stacks live in LDS, [entry][lane] so consecutive lanes hit consecutive banks;
+//  * a launch's constants (camera, table pointers, work geometry, claim parameters: LaunchConst) reach
+//    the tier-B kernels through a device copy that each workgroup stages in LDS ahead of its stacks;
+//    only what a walk step reads travels as kernel arguments (RenderArgs);
 //  * tier B (Philox per (pixel, sample)) shards by tiles with no data-path collective before the
 //    final framebuffer gather; tier A (the reference's per-column SplitMix stream) runs one lane per
 //    column;
@@ -68,7 +71,7 @@ struct rt_ctx {
   unsigned long long* d_counter = nullptr;
   double* d_partial = nullptr;  // tier-B chunk sums (grown on demand, at most kPartialCap)
   size_t partial_bytes = 0;
-  double* d_tail = nullptr;     // tier-B tail units' sample colours (RenderArgs::tail_buf), grown on demand
+  double* d_tail = nullptr;     // tier-B tail units' sample colours (LaunchConst::tail_buf), grown on demand
   size_t tail_bytes = 0;
   double* d_acc = nullptr;      // running per-pixel sums of a frame rendered in chunk batches
   size_t acc_bytes = 0;
@@ -285,6 +288,9 @@ constexpr size_t kPartialCap = 2ull << 30;
 // Dynamic LDS a CU's workgroup may take: 160 KiB less the replacement loop's static per-wave work
 // queues (16 waves x 8 B).
 constexpr size_t kLdsBudget = 160 * 1024 - 16 * 8;
+// The ctx's work-counter allocation: the counter's 256 bytes, then the device copy of the launch
+// constants (LaunchConst) that the tier-B kernels stage in LDS.
+constexpr size_t kCounterBytes = 256;
 
 // Occupancy target (waves per SIMD) of the render kernel; RTAMD_WAVES overrides (1..4) for A/B
 // measurements. The defaults (launch_philox) are measured.
@@ -340,8 +346,8 @@ int exact_launch(rt_ctx* c, bool shared_libm, const void** fn, size_t* bytes) {
   return RT_OK;
 }
 
-int launch_combine(rt_ctx* c, const RenderArgs& A, hipStream_t st) {
-  RenderArgs B = A;
+int launch_combine(rt_ctx* c, const LaunchConst& A, hipStream_t st) {
+  LaunchConst B = A;
   void* args[] = {&B};
   HIPCHK(hipLaunchKernel((const void*)combine_chunks, dim3((unsigned)((A.slab + 255) / 256)), dim3(256), args, 0,
                          st));
@@ -353,18 +359,13 @@ int launch_combine(rt_ctx* c, const RenderArgs& A, hipStream_t st) {
 // The launch's culling flags: the caller's, with the per-axis test alone for far-box worlds (rt_ctx::far_boxes).
 uint32_t cull(const rt_ctx* c, uint32_t flags) { return flags | (c->far_boxes ? RT_FLAG_REFERENCE_CULL : 0u); }
 
-int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int rank, int shards, uint8_t* d_rgb,
-                  double* d_lin, hipStream_t st, unsigned long long* d_work = nullptr,
-                  unsigned long long* d_prof = nullptr, const ChunkSpan& span = ChunkSpan{}) {
-  RenderArgs A{};
-  A.S = c->scene;
-  A.cam = *cam;
+// The work geometry of a tier-B launch in its constants: the frame's part (shard `rank` of `shards`, the
+// tiles, the sample chunks and their divisors) ...
+void fill_frame_geometry(LaunchConst& A, const rt_render_params* p, int rank, int shards, long long& per_shard) {
   A.W = p->width;
   A.H = p->height;
   A.spp = p->spp;
-  A.max_depth = p->max_depth;
-  A.flags = cull(c, p->flags);
-  long long tiles_total, per_shard, slab;
+  long long tiles_total, slab;
   geometry(p, A.tile, A.tiles_x, tiles_total, per_shard, slab);
   A.tiles_total = (int)tiles_total;
   A.shard_rank = rank;
@@ -381,6 +382,31 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   A.div_tp = make_udiv((uint32_t)(A.tile * A.tile));
   A.div_tiles_x = make_udiv((uint32_t)A.tiles_x);
   A.div_bpr = make_udiv((uint32_t)(A.tile >> 3));
+  A.div_chunk = make_udiv((uint32_t)A.chunk);
+}
+// ... and one launch's: `nk` chunks from the frame's chunk `k0`, the last `tail_items` work-items dealt
+// one sample per unit.
+void fill_batch_geometry(LaunchConst& A, int k0, int nk, long long tail_items) {
+  A.chunk_base = k0;
+  A.chunks = nk;
+  A.items_total = A.slab * nk;
+  const long long tail = std::min(A.items_total, tail_items);
+  A.tail_start = A.items_total - tail;
+  A.work_total = A.items_total + tail * (A.chunk - 1);
+  A.div_tile = make_udiv((uint32_t)(A.tile * A.tile * nk));
+}
+
+int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int rank, int shards, uint8_t* d_rgb,
+                  double* d_lin, hipStream_t st, unsigned long long* d_work = nullptr,
+                  unsigned long long* d_prof = nullptr, const ChunkSpan& span = ChunkSpan{}) {
+  LaunchConst A{};
+  A.S = c->scene;
+  A.cam = *cam;
+  A.max_depth = p->max_depth;
+  A.flags = cull(c, p->flags);
+  long long per_shard;
+  fill_frame_geometry(A, p, rank, shards, per_shard);
+  const long long slab = A.slab;
   A.seed = p->seed;
   A.counter = c->d_counter;
   A.work = d_work;
@@ -436,10 +462,24 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   // summed in sample order afterwards (tail_combine): the sums rt.h defines, whatever the dealing.
   // RTAMD_TAIL: tail items per CU (default 768, one per lane of 12 waves; 0: no tail).
   long long tail_items = 0;
-  A.div_chunk = make_udiv((uint32_t)A.chunk);
   auto units_of = [&](long long items) { return items + std::min(items, tail_items) * (A.chunk - 1); };
+  // The render kernel's own arguments (args[0] of `run`): what a walk step reads, and the constants'
+  // device copy, which lives behind the ctx's work counter (kCounterBytes) and is rewritten by
+  // launch_setup ahead of every launch, in stream order after the launch before.
+  RenderArgs R{};
   // one launch per chunk batch (stream-ordered; the events span all of them)
   auto run = [&](const void* fn, dim3 grid, dim3 block, size_t bytes, void** args) -> int {
+    unsigned char* counter_mem = reinterpret_cast<unsigned char*>(c->d_counter);
+    LaunchConst* d_lc = reinterpret_cast<LaunchConst*>(counter_mem + kCounterBytes);
+    R.S = A.S;
+    R.lc = d_lc;
+    R.seed = A.seed;
+    R.flags = A.flags;
+    R.trav_stop = A.trav_stop;
+    R.leaf_stop = A.leaf_stop;
+    R.box_first = A.box_first;
+    R.med_batch = A.med_batch;
+    R.prof = A.prof;
     // (work-unit indices are 32-bit on the device, and wave claims may run up to one batch per wave
     // past the end: keep 2^24 of headroom)
     if (units_of(slab * per_batch) >= (1ll << 32) - (1ll << 24))
@@ -458,20 +498,20 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
     for (int b0 = 0; b0 < chunks_total; b0 += per_batch) {
       const int nk = std::min(per_batch, chunks_total - b0);
       const int k0 = span_first + b0;  // the launch's first chunk of the frame
-      A.chunk_base = k0;
-      A.chunks = nk;
-      A.items_total = slab * nk;
-      A.tail_start = A.items_total - std::min(A.items_total, tail_items);
-      A.work_total = units_of(A.items_total);
-      A.div_tile = make_udiv((uint32_t)(A.tile * A.tile * nk));
+      fill_batch_geometry(A, k0, nk, tail_items);
       const bool last = b0 + nk == chunks_total;
       A.combine = (k0 > 0 ? 1 : 0) | (last && !span.keep ? 2 : 0);
-      HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), st));
+      {  // the constants' device copy, and the work counter back to 0
+        LaunchConst B = A;
+        void* sargs[] = {&B, &d_lc};
+        HIPCHK(hipLaunchKernel((const void*)launch_setup, dim3(1), dim3(64), sargs, 0, st));
+        HIPCHK(hipGetLastError());
+      }
       if (b0 == 0) HIPCHK(hipEventRecord(ev_begin, st));
       HIPCHK(hipLaunchKernel(fn, grid, block, args, bytes, st));  // (arguments are copied at launch)
       HIPCHK(hipGetLastError());
       if (A.tail_start < A.items_total) {
-        RenderArgs B = A;
+        LaunchConst B = A;
         void* targs[] = {&B};
         HIPCHK(hipLaunchKernel((const void*)tail_combine, dim3((unsigned)((A.items_total - A.tail_start + 255) / 256)),
                                dim3(256), targs, 0, st));
@@ -559,10 +599,11 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
     const int items = wide ? c->n_wnodes : c->n_nodes;
     const size_t rec = wide ? sizeof(rt_wnode) : sizeof(rt_node);
     const bool leaf_lds = wide && !env_off("RTAMD_LEAF_LDS");  // RTAMD_LEAF_LDS=0: leaves never in LDS
-    // LDS bytes at `w` waves per SIMD: the nodes, the lane stacks, and the wide walk's leaf table
-    // when it fits as well
+    // LDS bytes at `w` waves per SIMD: the launch constants, the nodes, the lane stacks, and the wide
+    // walk's leaf table when it fits as well
     auto lds_bytes = [&](int w, int& n_leaves) {
-      const size_t b = (size_t)items * rec + (size_t)(entries + side_ints) * (w * 256) * sizeof(int);
+      const size_t b =
+          (size_t)kLcBytes + (size_t)items * rec + (size_t)(entries + side_ints) * (w * 256) * sizeof(int);
       n_leaves = leaf_lds && b + (size_t)c->n_leaves * sizeof(rt_node) <= kLdsBudget ? c->n_leaves : 0;
       return b + (size_t)n_leaves * sizeof(rt_node);
     };
@@ -577,7 +618,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
       const void* fn = philox_kernel(var, loop, true, waves, false, n_leaves > 0);
       HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
       int n_items = items;
-      void* args[] = {&A, &n_items, (void*)&entries, &n_leaves};
+      void* args[] = {&R, &n_items, (void*)&entries, &n_leaves};
       c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u), loop, 1, n_leaves > 0, waves, c->cu_count,
                                       block, (int)bytes, A.work_total, A.chunk,
                                       (loop == 2 || (loop == 1 && c->mixed_wide)) ? c->n_wnodes : 0, batches, 0};
@@ -590,7 +631,8 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   // replacement loops: lane stacks (+ Side slots) in dynamic LDS, sized for this world's stack bound
   // (wide_node writes 3 slots)
   int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;
-  const size_t dyn = loop ? (size_t)(entries + side_ints) * RT_BLOCK * sizeof(int) : 0;
+  // (ahead of them the launch constants; the per-sample loop keeps both in static LDS)
+  const size_t dyn = loop ? (size_t)kLcBytes + (size_t)(entries + side_ints) * RT_BLOCK * sizeof(int) : 0;
   if (loop) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
   int bpc = 1;
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, RT_BLOCK, dyn));
@@ -600,7 +642,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (count ? F_COUNT : 0u), loop, 0, 0,
                                   count ? 1 : waves, grid, RT_BLOCK, (int)dyn, A.work_total, A.chunk,
                                   (loop == 2 || (loop == 1 && c->mixed_wide)) ? c->n_wnodes : 0, batches, 0};
-  void* args[] = {&A, &entries};
+  void* args[] = {&R, &entries};
   return run(fn, dim3(grid), dim3(RT_BLOCK), dyn, args);
 }
 
@@ -737,7 +779,7 @@ int rt_create(int device, rt_ctx** out) {
     HIPCHK(hipEventCreate(&c->ev_gather));
     HIPCHK(hipEventCreate(&c->ev_gathered));
     HIPCHK(hipEventCreate(&c->ev_asm));
-    HIPCHK(hipMalloc((void**)&c->d_counter, 256));
+    HIPCHK(hipMalloc((void**)&c->d_counter, kCounterBytes + sizeof(LaunchConst)));
     return RT_OK;
   };
   const int rc = init();
@@ -939,6 +981,38 @@ int rt_shard_geometry(const rt_render_params* p, int64_t* tiles_total, int64_t* 
   return RT_OK;
 }
 
+// Internal (rt_internal.h; no device needed): the launch constants' work geometry as launch_philox fills
+// it for shard p->shard_rank and a launch of `n_chunks` chunks from `chunk_first`, and the device's own
+// decomposition (work_unit) of the units [first, first + n) evaluated on the host.
+int rt_internal_work_units(const rt_render_params* p, int chunk_first, int n_chunks, long long tail_items,
+                           uint32_t first, int n, int32_t* out5, int64_t* out_slot, int64_t* out_totals) {
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!out5 || !out_slot))) return invalid("null output");
+  LaunchConst A{};
+  long long per_shard;
+  fill_frame_geometry(A, p, p->shard_rank, p->shard_count > 0 ? p->shard_count : 1, per_shard);
+  if (chunk_first < 0 || n_chunks < 1 || chunk_first + n_chunks > A.chunks || tail_items < 0)
+    return invalid("bad chunk span");
+  fill_batch_geometry(A, chunk_first, n_chunks, tail_items);
+  if (out_totals) {
+    out_totals[0] = A.work_total;
+    out_totals[1] = A.items_total;
+    out_totals[2] = A.tail_start;
+    out_totals[3] = A.slab;
+    out_totals[4] = A.chunk;
+  }
+  for (int i = 0; i < n; ++i) {
+    int px = -1, row = -1, s0 = 0, s1 = 0;
+    long long slot = -1;
+    const bool ok = work_unit(A, first + (uint32_t)i, px, row, s0, s1, slot);
+    int32_t* o = out5 + 5 * (size_t)i;
+    o[0] = ok, o[1] = px, o[2] = row, o[3] = s0, o[4] = s1;
+    out_slot[i] = slot;
+  }
+  return RT_OK;
+}
+
 int rt_render_shard_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, uint8_t* d_rgb, double* d_lin,
                           void* stream) {
   if (!c || !cam || !d_rgb) return invalid("null argument");
@@ -1040,7 +1114,7 @@ int rt_render(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, cons
     if ((rc = grow(c, c->fb_gens, sizeof(uint64_t) * 2 * (size_t)p.width))) return rc;
     uint64_t* d_gens = (uint64_t*)c->fb_gens.p;
     HIPCHK(hipMemcpyAsync(d_gens, col_gens, sizeof(uint64_t) * 2 * (size_t)p.width, hipMemcpyHostToDevice, st));
-    RenderArgs A{};
+    LaunchConst A{};
     A.S = c->scene;
     A.cam = *cam;
     A.W = p.width;
@@ -1266,7 +1340,7 @@ int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb, double* out_lin, rt_frame_st
   DEVICE_SCOPE(c->device);
   // (nothing rendered since the last resolve: the device still holds that preview, and its stats repeat)
   if (f->last.chunks_done != f->chunks_done) {
-    RenderArgs A{};
+    LaunchConst A{};
     A.W = f->p.width;
     A.H = f->p.height;
     long long tt, ps, slab;
@@ -1440,7 +1514,7 @@ int rt_debug_exact_trace(rt_ctx* c, const rt_camera* cam, const rt_render_params
   HIPCHK(hipMalloc(&trn.p, sizeof(int)));
   HIPCHK(hipMemcpy(gens.p, col_gens, sizeof(uint64_t) * 2 * (size_t)p.width, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(trn.p, 0, sizeof(int)));
-  RenderArgs A{};
+  LaunchConst A{};
   A.S = c->scene;
   A.cam = *cam;
   A.W = p.width;
