@@ -184,6 +184,14 @@ typedef struct rt_camera {
  *                from 0. (The chunks are the device's work-items; a definition fixed by
  *                (width, height, spp) keeps the image independent of scheduling and shard
  *                count.) Embarrassingly parallel.
+ *                A tier-B path ends once its throughput is NaN in all three channels (the Lambertian
+ *                mixture quirk's 0 / 0, src/Lib.hs:823-836, in a world without lights): background,
+ *                emission and depth exhaustion all give throughput * x = (NaN, NaN, NaN) from there,
+ *                and the draws the rest of the path would make belong to this sample's stream alone,
+ *                so the sample adds throughput * 0 at once. Every sample is still started, counted
+ *                and summed in order; the image is the one full paths give (NaNs by mask). Zero
+ *                throughput, or one or two NaN channels, end nothing. Tier A traces every path to its
+ *                end: a column's stream runs through every draw of every sample.
  *                ConstantMedium (src/Lib.hs:1053-1080) in tier B: its draw is not the stream's next
  *                but the first word of the block at counter {stream words consumed so far, sample,
  *                pixel_id, 2^31 | key}, key = the occurrence's preorder rank among the medium

@@ -350,7 +350,14 @@ __device__ __forceinline__ void philox_loop(const RenderArgs& A, const LaunchCon
       s1 = stamp();
       s2 = s1;
     }
-    const bool ended = segment<F>(A, S, L.S, ray, thr, depth, g, stk, contrib, cnt, stride, &s2);
+    bool ended = segment<F>(A, S, L.S, ray, thr, depth, g, stk, contrib, cnt, stride, &s2);
+    // the dead-path cut (philox_loop2 has the reasoning): a throughput that is NaN in all three channels
+    // decides the sample's colour, thr * 0 as at depth 0. Here, after segment(), not in it: tier A
+    // (render_exact) shares segment() and shade_hit() and must trace every path to its end.
+    if (!ended && thr.x != thr.x && thr.y != thr.y && thr.z != thr.z) {
+      contrib = vmul(thr, v3(0.0, 0.0, 0.0));
+      ended = true;
+    }
     if constexpr ((F & F_COUNT) != 0) {
       const unsigned long long s3 = stamp();
       ph_acq += s1 - s0;
@@ -496,11 +503,10 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
     }
     // ---- shade finished walks, then set up the next walk for every lane that is not walking
     // exact tie, or a NaN-t rect hit in a re-bounded subtree (trav_take: `lite` in a first walk): redo
-    // this walk as the reference does (once) — unless the path's throughput is NaN in every channel
-    // already: its colour is NaN whichever leaf the reference's order picks (NaN * anything, including
-    // the background's 0, is NaN), and a tier-B sample's draws reach no other sample. (NaN-t hits come
-    // from the Lambertian quirk's +x ray in a box top's plane, whose pdf is 0 / 0: DESIGN.md §4.3.)
-    if (ready && (t.tie || (kRefMixed<F> && t.lite)) && !t.redo && !all_nan3(thr)) {
+    // this walk as the reference does (once). (NaN-t hits come from the Lambertian quirk's +x ray in a
+    // box top's plane, whose pdf is 0 / 0: DESIGN.md §4.3. A walking path's throughput is never NaN in
+    // every channel: such a path ends where it is shaded, below.)
+    if (ready && (t.tie || (kRefMixed<F> && t.lite)) && !t.redo) {
       ready = false;
       if constexpr ((F & F_COUNT) != 0) ++cnt.ties;
       trav_redo<F>(t, L.S.world_ref, INFINITY);
@@ -522,7 +528,16 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
       V3 th = thr;
       if (shade_hit<F>(L.S, got, h, ray, th, depth, g, contrib, cnt)) {
         end_sample(contrib);
-      } else if (depth <= 0) {  // rayColor's d <= 0 -> black (thr * 0 keeps a NaN throughput NaN)
+      } else if (depth <= 0 || all_nan3(th)) {
+        // rayColor's d <= 0 -> black (thr * 0 keeps a NaN throughput NaN) — and the dead-path cut: once
+        // the throughput is NaN in all three channels (the Lambertian quirk's 0 / 0), every
+        // way the path can end gives (NaN, NaN, NaN): thr * background, thr * emitted, thr * 0 at depth 0.
+        // A tier-B sample draws from its own (pixel, sample) stream, so the draws the rest of the path
+        // would make reach no other sample: the sample ends here with the same thr * 0. Exactly "all
+        // three": a zero throughput is not decided (a later 0 * NaN factor turns it into NaN), and with
+        // one or two NaN channels the others still carry colour. Tier B only, and so not in segment() or
+        // shade_hit(), which render_exact shares: tier A's column stream runs through every draw of
+        // every sample, so tier A traces every path to its end.
         end_sample(vmul(th, v3(0.0, 0.0, 0.0)));
       } else {  // next segment of the same path
         thr = th;
