@@ -184,6 +184,10 @@ typedef struct rt_camera {
  *                from 0. (The chunks are the device's work-items; a definition fixed by
  *                (width, height, spp) keeps the image independent of scheduling and shard
  *                count.) Embarrassingly parallel.
+ *                A progressive frame opened with RT_FRAME_MOMENTS also keeps, per pixel and channel,
+ *                Q = sum over chunks of (S_k * S_k) / (double)n_k in chunk order from 0 (S_k the chunk's
+ *                sum, n_k its sample count): the second moment its error estimate rests on, defined
+ *                with the frames below.
  *                A tier-B path ends once its throughput is NaN in all three channels (the Lambertian
  *                mixture quirk's 0 / 0, src/Lib.hs:823-836, in a world without lights): background,
  *                emission and depth exhaustion all give throughput * x = (NaN, NaN, NaN) from there,
@@ -569,7 +573,46 @@ int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
  * CH = rt_sample_chunk(pixels, spp); 0 <= chunks_done <= chunks_total; payload bytes = pixels * 24;
  * length = 288 + payload bytes. Else RT_E_INVALID.
  *
- * Not covered: sharded or multi-device frames, per-pixel error estimates, adaptive sampling, and
+ * Per-pixel error estimates (frames opened with RT_FRAME_MOMENTS). A pixel's samples are independent
+ * Philox streams, so the spread of its chunk sums estimates its variance (batch means). Besides the
+ * running sum S = sum_k S_k, a tracked frame keeps per pixel and channel
+ *     Q = sum_k (S_k * S_k) / (double)n_k,   added in chunk order from 0,
+ * S_k chunk k's sum and n_k its sample count (CH, or fewer for the short last chunk; k is the frame's
+ * chunk index). Each term is computed as written in IEEE fp64: multiply, divide, then add (no
+ * contraction). Like the sums, Q is a fixed function of (scene, camera, params), independent of step
+ * pattern and chunk batching, and tracking changes no sum: a tracked frame's image and blob are the
+ * untracked frame's bit for bit. After K >= 2 chunks and N samples, per channel, in this order:
+ *     t = (S * S) / N;   d = Q - t, set to 0 when d < 0 (rounding only);   se = sqrt((d / (K - 1)) / N)
+ * se is the standard error of the pixel's mean S / N; the estimate of the variance under it is unbiased,
+ * E[sum_k S_k^2 / n_k - S^2 / N] = (K - 1) sigma^2. A pixel is non-finite when any se channel is not
+ * finite (NaN sums of the Lambertian-mixture quirk, infinite sums). A finite pixel is converged under
+ * (abs_tol, rel_tol) when se_c <= abs_tol + rel_tol * |S_c / N| holds for all three channels.
+ *
+ * open_ex     rt_frame_open with frame flags (rt_frame_open = flags 0; unknown bits: RT_E_INVALID). With
+ *             RT_FRAME_MOMENTS the frame also owns Q (device memory, slab order, zeroed, 24 bytes per
+ *             pixel of the tile-padded image) and advance folds the Q terms with the sums.
+ * moments     Q in image order, H*W*3 doubles (drains the frame's queued work). RT_E_STATE when the frame
+ *             does not track moments or no chunk has been rendered.
+ * restore_ex  rt_frame_restore plus the moments saved with the blob (H*W*3 doubles, image order, as
+ *             rt_frame_moments wrote them when the blob was saved): a tracked frame that continues exactly
+ *             where the saved one stopped. moments == NULL: rt_frame_restore (an untracked frame). The
+ *             version-1 blob has no room for Q and is unchanged; keeping a blob and its moments together
+ *             is the caller's responsibility (moments of another save give a frame whose Q is not rt.h's).
+ * error       The error map and its summary at any point of a tracked frame with chunks_done >= 2, at a
+ *             tolerance (NULL: {0, 0}; a negative or NaN value: RT_E_INVALID). out_se (H*W*3 doubles, image
+ *             order) and out may each be NULL. RT_E_STATE for an untracked frame, a frame whose ctx's
+ *             scene was replaced, or chunks_done < 2. Independent of rt_frame_resolve: it leaves
+ *             bytes_changed and the stored preview alone.
+ * error stats pixels = H*W; nonfinite_pixels; unconverged_pixels counts finite pixels only; max_se and
+ *             mean_se run over the channels of finite pixels (0 when there are none). The counts and
+ *             max_se are exact. mean_se is added in a fixed order without floating-point atomics, so
+ *             every call returns the same value; it agrees with the sequential fp64 sum to 1e-12 relative.
+ * rt_error_estimate  The same per-pixel function on the host alone (no device), over image-order arrays:
+ *             an error map offline from a blob's payload and the saved moments. mean_se is the
+ *             sequential sum in pixel and channel order. chunks_done < 2, pixels <= 0, samples_done <
+ *             chunks_done, a null array or a bad tolerance: RT_E_INVALID.
+ *
+ * Not covered: sharded or multi-device frames, adaptive sampling, error estimates for tier A, and
  * extending a frame past its spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its per-chunk meaning.
  */
 #define RT_FRAME_BLOB_VERSION 1u
@@ -604,6 +647,27 @@ int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len);
 int rt_frame_restore(rt_ctx* ctx, const void* buf, size_t len, rt_frame** out);
 int rt_frame_blob_info(const void* buf, size_t len, rt_frame_blob_desc* out);
 void rt_frame_close(rt_frame* f);
+#define RT_FRAME_MOMENTS 1u /* frame flag: keep Q, the per-pixel second moment of the chunk sums (above) */
+typedef struct rt_error_tol {
+    double abs_tol;
+    double rel_tol;
+} rt_error_tol; /* 16 bytes */
+typedef struct rt_error_stats {
+    int32_t chunks_done;
+    int32_t samples_done;
+    int64_t pixels;
+    int64_t nonfinite_pixels;
+    int64_t unconverged_pixels;
+    double max_se;
+    double mean_se;
+} rt_error_stats; /* 48 bytes */
+int rt_frame_open_ex(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, uint32_t frame_flags,
+                     rt_frame** out);
+int rt_frame_moments(rt_frame* f, double* out_q);
+int rt_frame_restore_ex(rt_ctx* ctx, const void* buf, size_t len, const double* moments, rt_frame** out);
+int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_error_stats* out);
+int rt_error_estimate(const double* sums, const double* moments, int64_t pixels, int chunks_done,
+                      int samples_done, const rt_error_tol* tol, double* out_se, rt_error_stats* out);
 /* The fingerprint rt_upload_scene records for a descriptor (host only; the blob's field at 272). */
 int rt_scene_fingerprint(const rt_scene_desc* desc, uint64_t* out);
 /* The chunking of a tier-B frame of `pixels` pixels at `spp` samples (host only): *out_chunk =

@@ -15,6 +15,7 @@
 
 #include "rt.h"
 #include "rt_device.h"
+#include "rt_error.h"
 #include "rt_internal.h"
 #include "rt_trace.h"
 
@@ -747,15 +748,33 @@ __global__ void __launch_bounds__(256) tail_combine(LaunchConst A) {
 
 // Tier B: a slab pixel's chunk sums added in chunk order, then averaged and stored (rt.h); with chunk
 // batches, each batch's chunks are added to the running sum of the batches before it.
-__global__ void __launch_bounds__(256) combine_chunks(LaunchConst A) {
+// MOMENTS (a tracked progressive frame, RT_FRAME_MOMENTS): the same additions to the sums, and the chunks'
+// (S_k * S_k) / n_k added in chunk order to the pixel's second moments Q (`moments`, [slab pixel][3]; rt.h),
+// n_k the sample count of the frame's chunk chunk_base + k.
+template <bool MOMENTS>
+__device__ __forceinline__ void combine_body(const LaunchConst& A, double* moments) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= A.slab) return;
   int px, row;
   if (!work_pixel(A, (uint32_t)idx, px, row)) return;  // outside the image: never assembled
   V3 acc = (A.combine & 1) ? vload(A.acc + idx * 3) : v3(0, 0, 0);
+  V3 mom = v3(0, 0, 0);
+  if constexpr (MOMENTS) {
+    if (A.combine & 1) mom = vload(moments + idx * 3);
+  }
   for (int k = 0; k < A.chunks; ++k) {
     const double* q = A.partial + ((long long)k * A.slab + idx) * 3;
     acc = acc + v3(q[0], q[1], q[2]);
+    if constexpr (MOMENTS) {
+      const int s0 = (A.chunk_base + k) * A.chunk;
+      const double n = (double)(A.spp - s0 < A.chunk ? A.spp - s0 : A.chunk);
+      mom = mom + v3((q[0] * q[0]) / n, (q[1] * q[1]) / n, (q[2] * q[2]) / n);
+    }
+  }
+  if constexpr (MOMENTS) {
+    moments[idx * 3 + 0] = mom.x;
+    moments[idx * 3 + 1] = mom.y;
+    moments[idx * 3 + 2] = mom.z;
   }
   if (A.combine & 2) {
     store_pixel(A, idx, divide(acc, (double)A.spp));
@@ -764,6 +783,10 @@ __global__ void __launch_bounds__(256) combine_chunks(LaunchConst A) {
     A.acc[idx * 3 + 1] = acc.y;
     A.acc[idx * 3 + 2] = acc.z;
   }
+}
+__global__ void __launch_bounds__(256) combine_chunks(LaunchConst A) { combine_body<false>(A, nullptr); }
+__global__ void __launch_bounds__(256) combine_chunks_moments(LaunchConst A, double* moments) {
+  combine_body<true>(A, moments);
 }
 
 // ---------------------------------------------------------------- tier A: the reference's stream
@@ -913,6 +936,83 @@ __global__ void __launch_bounds__(256) frame_scatter(const double* image, double
   sums[dst * 3 + 0] = image[i * 3 + 0];
   sums[dst * 3 + 1] = image[i * 3 + 1];
   sums[dst * 3 + 2] = image[i * 3 + 2];
+}
+
+// A tracked frame's error map and summary (rt.h): one thread per image pixel reads its sums and moments
+// (slab order, through frame_slot), computes se[3] (rt::pixel_error, the host's text) and stores it in image
+// order when `out_se` is given. acc[0] += non-finite pixels, acc[1] += finite unconverged pixels (ballots
+// per wave, LDS over the block's 4 waves, one atomic per block and counter, as frame_resolve's counts);
+// acc[2] = max se over the finite pixels' channels, as the value's bit pattern (non-negative finite doubles
+// order as unsigned integers: a lane-shuffle max per wave, LDS, one atomicMax per block); and the block's
+// sum of those se in a fixed order (a pixel's channels in order, a wave's lanes by halving shuffles, the
+// waves in wave order) to block_sums[blockIdx.x]: frame_error_sum adds them, so the total has no
+// floating-point atomic in it and repeats.
+__global__ void __launch_bounds__(256) frame_error(const double* sums, const double* moments, double* out_se, int W,
+                                                   int H, int tile, int tiles_x, int chunks, int samples,
+                                                   double abs_tol, double rel_tol, unsigned long long* acc,
+                                                   double* block_sums) {
+  __shared__ unsigned wave_bad[4], wave_open[4];
+  __shared__ unsigned long long wave_max[4];
+  __shared__ double wave_sum[4];
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool bad = false, open = false;
+  double sum = 0.0;
+  unsigned long long top = 0ull;
+  if (i < (long long)W * H) {
+    const long long slot = frame_slot(i, W, tile, tiles_x) * 3;
+    const double s[3] = {sums[slot], sums[slot + 1], sums[slot + 2]};
+    const double q[3] = {moments[slot], moments[slot + 1], moments[slot + 2]};
+    double se[3];
+    const int cls = rt::pixel_error(s, q, chunks, samples, abs_tol, rel_tol, se);
+    if (out_se) {
+      out_se[i * 3 + 0] = se[0];
+      out_se[i * 3 + 1] = se[1];
+      out_se[i * 3 + 2] = se[2];
+    }
+    bad = cls == rt::kPixelNonFinite;
+    open = cls == rt::kPixelUnconverged;
+    if (!bad) {
+      sum = (se[0] + se[1]) + se[2];
+      const double m = fmax(fmax(se[0], se[1]), se[2]);
+      top = (unsigned long long)__double_as_longlong(m);
+    }
+  }
+  const unsigned n_bad = (unsigned)__popcll(__ballot(bad)), n_open = (unsigned)__popcll(__ballot(open));
+  for (int off = 32; off > 0; off >>= 1) {
+    sum = sum + __shfl_down(sum, off, 64);
+    const unsigned long long other = __shfl_down(top, off, 64);
+    top = other > top ? other : top;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    wave_bad[w] = n_bad;
+    wave_open[w] = n_open;
+    wave_max[w] = top;
+    wave_sum[w] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned nb = wave_bad[0] + wave_bad[1] + wave_bad[2] + wave_bad[3];
+    const unsigned no = wave_open[0] + wave_open[1] + wave_open[2] + wave_open[3];
+    unsigned long long m = wave_max[0];
+    for (int w = 1; w < 4; ++w) m = wave_max[w] > m ? wave_max[w] : m;
+    if (nb) atomicAdd(&acc[0], (unsigned long long)nb);
+    if (no) atomicAdd(&acc[1], (unsigned long long)no);
+    if (m) atomicMax(&acc[2], m);
+    block_sums[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+  }
+}
+
+// frame_error's block sums added in a fixed order by one block: thread t adds blocks t, t + 256, ... in
+// block order, then the threads' sums fold as a block's do (lanes by halving shuffles, waves in wave order).
+__global__ void __launch_bounds__(256) frame_error_sum(const double* block_sums, int blocks, double* out) {
+  __shared__ double wave_sum[4];
+  double sum = 0.0;
+  for (int b = threadIdx.x; b < blocks; b += 256) sum = sum + block_sums[b];
+  for (int off = 32; off > 0; off >>= 1) sum = sum + __shfl_down(sum, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
 }
 
 // ---------------------------------------------------------------- debug: closest hits

@@ -116,6 +116,12 @@ struct rt_frame {
   double* d_lin = nullptr;   // the last linear preview, H*W*3
   double* d_stage = nullptr; // save's and restore's image-order copy of the sums, H*W*3, on first use
   unsigned long long* d_counts = nullptr;  // frame_resolve's {nan_pixels, bytes_changed}
+  // RT_FRAME_MOMENTS: the second moments Q of the chunk sums, [slab pixel][3] like d_sum (else null);
+  // frame_error's image-order map, H*W*3, and its {non-finite, unconverged, max bits, sum} followed by one
+  // partial sum per block, both on first use
+  double* d_q = nullptr;
+  double* d_se = nullptr;
+  unsigned long long* d_err = nullptr;
   rt_frame_stats last{};     // the last resolve's counts (a poll with nothing new rendered repeats them)
   // one event pair per advance since the last resolve (kernel_ms); `used` of them are pending
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -130,6 +136,7 @@ struct ChunkSpan {
   int count = -1;           // -1: every chunk of the frame
   double* acc = nullptr;    // running sums between launches; nullptr: the ctx's d_acc, grown on demand
   bool keep = false;        // keep the running sums in `acc` after the last chunk (no image is stored)
+  double* moments = nullptr;  // a tracked frame's second moments, folded with the sums (combine_chunks_moments)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;  // around the render launches; nullptr: the ctx's ev0 / ev1
 };
 
@@ -346,11 +353,11 @@ int exact_launch(rt_ctx* c, bool shared_libm, const void** fn, size_t* bytes) {
   return RT_OK;
 }
 
-int launch_combine(rt_ctx* c, const LaunchConst& A, hipStream_t st) {
+int launch_combine(rt_ctx* c, const LaunchConst& A, hipStream_t st, double* moments) {
   LaunchConst B = A;
-  void* args[] = {&B};
-  HIPCHK(hipLaunchKernel((const void*)combine_chunks, dim3((unsigned)((A.slab + 255) / 256)), dim3(256), args, 0,
-                         st));
+  void* args[] = {&B, &moments};  // (combine_chunks takes the first alone)
+  const void* fn = moments ? (const void*)combine_chunks_moments : (const void*)combine_chunks;
+  HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((A.slab + 255) / 256)), dim3(256), args, 0, st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_done, st));
   return RT_OK;
@@ -518,7 +525,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
         HIPCHK(hipGetLastError());
       }
       if (last) HIPCHK(hipEventRecord(ev_end, st));
-      const int rc = launch_combine(c, A, st);
+      const int rc = launch_combine(c, A, st, span.moments);
       if (rc) return rc;
     }
     return RT_OK;
@@ -1235,6 +1242,9 @@ void frame_free(rt_frame* f) {
   (void)hipFree(f->d_lin);
   (void)hipFree(f->d_stage);
   (void)hipFree(f->d_counts);
+  (void)hipFree(f->d_q);
+  (void)hipFree(f->d_se);
+  (void)hipFree(f->d_err);
   for (auto& e : f->events) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
@@ -1242,8 +1252,11 @@ void frame_free(rt_frame* f) {
   delete f;
 }
 
-// A frame of `p` on c with zero sums and a zero previous preview, registered on the ctx.
-int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, const char* what, rt_frame** out) {
+// A frame of `p` on c with zero sums and a zero previous preview, registered on the ctx; with
+// RT_FRAME_MOMENTS in `frame_flags`, zero second moments too.
+int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, uint32_t frame_flags, const char* what,
+              rt_frame** out) {
+  if (frame_flags & ~RT_FRAME_MOMENTS) return invalid(std::string(what) + ": unknown frame flag");
   rt_render_params p = *pin;  // whole image: the shard fields are ignored
   p.shard_rank = 0;
   p.shard_count = 1;
@@ -1275,6 +1288,10 @@ int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, cons
     HIPCHK(hipMalloc((void**)&f->d_counts, 2 * sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(f->d_sum, 0, sums, c->stream));
     HIPCHK(hipMemsetAsync(f->d_rgb, 0, img, c->stream));
+    if (frame_flags & RT_FRAME_MOMENTS) {
+      HIPCHK(hipMalloc((void**)&f->d_q, sums));
+      HIPCHK(hipMemsetAsync(f->d_q, 0, sums, c->stream));
+    }
     return RT_OK;
   };
   if ((rc = init())) {
@@ -1293,7 +1310,13 @@ extern "C" {
 int rt_frame_open(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, rt_frame** out) {
   if (!c || !cam || !p || !out) return invalid("rt_frame_open: null argument");
   *out = nullptr;
-  return frame_new(c, cam, p, "rt_frame_open", out);
+  return frame_new(c, cam, p, 0, "rt_frame_open", out);
+}
+
+int rt_frame_open_ex(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, uint32_t frame_flags, rt_frame** out) {
+  if (!c || !cam || !p || !out) return invalid("rt_frame_open_ex: null argument");
+  *out = nullptr;
+  return frame_new(c, cam, p, frame_flags, "rt_frame_open_ex", out);
 }
 
 int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
@@ -1319,6 +1342,7 @@ int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
   span.count = n;
   span.acc = f->d_sum;
   span.keep = true;
+  span.moments = f->d_q;
   span.ev_begin = f->events[f->used].first;
   span.ev_end = f->events[f->used].second;
   rc = launch_philox(c, &f->cam, &f->p, 0, 1, nullptr, nullptr, c->stream, nullptr, nullptr, span);
@@ -1412,6 +1436,10 @@ int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len) {
 }
 
 int rt_frame_restore(rt_ctx* c, const void* buf, size_t len, rt_frame** out) {
+  return rt_frame_restore_ex(c, buf, len, nullptr, out);
+}
+
+int rt_frame_restore_ex(rt_ctx* c, const void* buf, size_t len, const double* moments, rt_frame** out) {
   if (!c || !out) return invalid("rt_frame_restore: null argument");
   *out = nullptr;
   rt_frame_blob_desc b;
@@ -1421,18 +1449,23 @@ int rt_frame_restore(rt_ctx* c, const void* buf, size_t len, rt_frame** out) {
   if (b.scene_fingerprint != c->fingerprint || b.upload_flags != c->upload_flags)
     return state_error("rt_frame_restore: the blob was saved over another scene (fingerprint or upload flags differ)");
   rt_frame* f = nullptr;
-  if ((rc = frame_new(c, &b.camera, &b.params, "rt_frame_restore", &f))) return rc;
+  if ((rc = frame_new(c, &b.camera, &b.params, moments ? RT_FRAME_MOMENTS : 0u, "rt_frame_restore", &f))) return rc;
   auto fill = [&]() -> int {
     DEVICE_SCOPE(c->device);
     HIPCHK(hipMalloc((void**)&f->d_stage, (size_t)b.payload_bytes));
-    HIPCHK(hipMemcpy(f->d_stage, (const uint8_t*)buf + RT_FRAME_BLOB_HEADER, (size_t)b.payload_bytes, hipMemcpyHostToDevice));
     int tile, tiles_x;
     long long tt, ps, slab;
     geometry(&f->p, tile, tiles_x, tt, ps, slab);
-    hipLaunchKernelGGL(frame_scatter, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
-                       (const double*)f->d_stage, f->d_sum, f->p.width, f->p.height, tile, tiles_x);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
+    // the payload, then the caller's moments (the same size and order), each through the stage buffer
+    const void* src[2] = {(const uint8_t*)buf + RT_FRAME_BLOB_HEADER, moments};
+    double* dst[2] = {f->d_sum, f->d_q};
+    for (int i = 0; i < (moments ? 2 : 1); ++i) {
+      HIPCHK(hipMemcpy(f->d_stage, src[i], (size_t)b.payload_bytes, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(frame_scatter, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
+                         (const double*)f->d_stage, dst[i], f->p.width, f->p.height, tile, tiles_x);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
     return RT_OK;
   };
   if ((rc = fill())) {
@@ -1441,6 +1474,75 @@ int rt_frame_restore(rt_ctx* c, const void* buf, size_t len, rt_frame** out) {
   }
   f->chunks_done = b.chunks_done;
   *out = f;
+  return RT_OK;
+}
+
+int rt_frame_moments(rt_frame* f, double* out_q) {
+  int rc = frame_live(f, "rt_frame_moments");
+  if (rc) return rc;
+  if (!out_q) return invalid("rt_frame_moments: null argument");
+  if (!f->d_q) return state_error("rt_frame_moments: the frame was opened without RT_FRAME_MOMENTS");
+  if (f->chunks_done == 0) return state_error("rt_frame_moments: no chunk rendered yet");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  const size_t bytes = sizeof(double) * 3 * (size_t)f->npx;
+  if (!f->d_stage) HIPCHK(hipMalloc((void**)&f->d_stage, bytes));
+  int tile, tiles_x;
+  long long tt, ps, slab;
+  geometry(&f->p, tile, tiles_x, tt, ps, slab);
+  hipLaunchKernelGGL(assemble<double>, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
+                     (const double*)f->d_q, f->d_stage, f->p.width, f->p.height, tile, tiles_x, 1, slab);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(out_q, f->d_stage, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_error_stats* out) {
+  int rc = frame_live(f, "rt_frame_error");
+  if (rc) return rc;
+  double abs_tol, rel_tol;
+  if (!rt::error_tol(tol, abs_tol, rel_tol)) return invalid("rt_frame_error: abs_tol and rel_tol must be >= 0 and not NaN");
+  if (!f->d_q) return state_error("rt_frame_error: the frame was opened without RT_FRAME_MOMENTS");
+  if (f->chunks_done < 2) return state_error("rt_frame_error: the estimate needs at least 2 chunks");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  const int blocks = (int)((f->npx + 255) / 256);
+  const size_t map_bytes = sizeof(double) * 3 * (size_t)f->npx;
+  if (out_se && !f->d_se) HIPCHK(hipMalloc((void**)&f->d_se, map_bytes));  // (kept, as d_stage is)
+  if (!f->d_err) HIPCHK(hipMalloc((void**)&f->d_err, sizeof(unsigned long long) * (4 + (size_t)blocks)));
+  int W = f->p.width, H = f->p.height, tile, tiles_x;
+  long long tt, ps, slab;
+  geometry(&f->p, tile, tiles_x, tt, ps, slab);
+  int chunks = f->chunks_done, samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
+  const double *d_sum = f->d_sum, *d_q = f->d_q;
+  double* d_se = out_se ? f->d_se : nullptr;
+  unsigned long long* d_acc = f->d_err;
+  double *d_block = reinterpret_cast<double*>(f->d_err + 4), *d_total = reinterpret_cast<double*>(f->d_err + 3);
+  HIPCHK(hipMemsetAsync(d_acc, 0, 4 * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(frame_error, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_sum, d_q, d_se, W, H, tile, tiles_x,
+                     chunks, samples, abs_tol, rel_tol, d_acc, d_block);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(frame_error_sum, dim3(1), dim3(256), 0, c->stream, (const double*)d_block, blocks, d_total);
+  HIPCHK(hipGetLastError());
+  unsigned long long acc[4] = {0, 0, 0, 0};  // (copied in stream order: one wait for the kernels and the summary)
+  HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (out_se) HIPCHK(hipMemcpy(out_se, f->d_se, map_bytes, hipMemcpyDeviceToHost));
+  if (out) {
+    rt_error_stats st{};
+    st.chunks_done = chunks;
+    st.samples_done = samples;
+    st.pixels = (int64_t)f->npx;
+    st.nonfinite_pixels = (int64_t)acc[0];
+    st.unconverged_pixels = (int64_t)acc[1];
+    double total;
+    std::memcpy(&st.max_se, &acc[2], sizeof(double));
+    std::memcpy(&total, &acc[3], sizeof(double));
+    const int64_t finite = st.pixels - st.nonfinite_pixels;
+    st.mean_se = finite ? total / (double)(3 * finite) : 0.0;
+    *out = st;
+  }
   return RT_OK;
 }
 

@@ -34,6 +34,7 @@ RT_FLAG_REFERENCE_CULL = 2
 RT_FLAG_NAN_ZERO = 4  # parity diagnostic: NaN sample channels add 0 (rt.h)
 RT_FLAG_SHARED_LIBM = 8  # tier A parity aid: the portable include/rt_libm.h transcendentals on both sides
 RT_UPLOAD_REFERENCE_BVH = 1
+RT_FRAME_MOMENTS = 1  # rt_frame_open_ex: keep the chunk sums' second moments (per-pixel error estimates)
 RT_DEBUG_RESUMABLE = 4  # rt_debug_closest_hits: the render loop's resumable binary walk
 RT_DEBUG_WIDE = 8       # rt_debug_closest_hits: the resumable walk over the 4-wide fp32-box tree
 RT_DEBUG_QNODE = 16     # ... over its quantised form (rt_qnode) with sphere quadruples (spheres-only worlds)
@@ -135,7 +136,18 @@ class rt_frame_blob_desc(C.Structure):
                 ("payload_bytes", C.c_uint64)]
 
 
+class rt_error_tol(C.Structure):
+    _fields_ = [("abs_tol", C.c_double), ("rel_tol", C.c_double)]
+
+
+class rt_error_stats(C.Structure):
+    _fields_ = [("chunks_done", C.c_int32), ("samples_done", C.c_int32), ("pixels", C.c_int64),
+                ("nonfinite_pixels", C.c_int64), ("unconverged_pixels", C.c_int64), ("max_se", C.c_double),
+                ("mean_se", C.c_double)]
+
+
 assert C.sizeof(rt_frame_stats) == 40 and C.sizeof(rt_frame_blob_desc) == 288
+assert C.sizeof(rt_error_tol) == 16 and C.sizeof(rt_error_stats) == 48
 assert C.sizeof(rt_node) == 64 and C.sizeof(rt_material) == 16 and C.sizeof(rt_texture) == 48
 assert C.sizeof(rt_perlin) == 9216 and C.sizeof(rt_camera) == 192 and C.sizeof(rt_render_params) == 48
 assert C.sizeof(rt_scene_desc) == 112
@@ -156,6 +168,7 @@ EXPORTED = [
     "rt_debug_exact_trace", "rt_quantize_wide",
     "rt_frame_open", "rt_frame_advance", "rt_frame_resolve", "rt_frame_save", "rt_frame_restore",
     "rt_frame_blob_info", "rt_frame_close", "rt_scene_fingerprint", "rt_frame_chunking",
+    "rt_frame_open_ex", "rt_frame_moments", "rt_frame_restore_ex", "rt_frame_error", "rt_error_estimate",
 ]
 
 # include/rt_wide.h: one 4-wide node (128 B)
@@ -253,6 +266,11 @@ def lib() -> C.CDLL:
             "rt_frame_close": (None, [C.c_void_p]),
             "rt_scene_fingerprint": (I, [P(rt_scene_desc), P(U64)]),
             "rt_frame_chunking": (I, [C.c_int64, I, P(I), P(I)]),
+            "rt_frame_open_ex": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), C.c_uint32, P(C.c_void_p)]),
+            "rt_frame_moments": (I, [C.c_void_p, P(D)]),
+            "rt_frame_restore_ex": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(D), P(C.c_void_p)]),
+            "rt_frame_error": (I, [C.c_void_p, P(rt_error_tol), P(D), P(rt_error_stats)]),
+            "rt_error_estimate": (I, [P(D), P(D), C.c_int64, I, I, P(rt_error_tol), P(D), P(rt_error_stats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -603,14 +621,16 @@ class Context:
                "rt_upload_scene")
         self._scene = scene
 
-    def open_frame(self, cam: rt_camera, params: rt_render_params) -> "ProgressiveFrame":
-        """rt_frame_open: a progressive tier-B frame of this ctx's scene (rtamd.progressive)."""
-        return ProgressiveFrame.open(self, cam, params)
+    def open_frame(self, cam: rt_camera, params: rt_render_params, moments: bool = False) -> "ProgressiveFrame":
+        """rt_frame_open: a progressive tier-B frame of this ctx's scene (rtamd.progressive); with
+        `moments`, one that tracks the second moments its error estimate needs (RT_FRAME_MOMENTS)."""
+        return ProgressiveFrame.open(self, cam, params, moments=moments)
 
-    def restore_frame(self, blob: bytes) -> "ProgressiveFrame":
+    def restore_frame(self, blob: bytes, moments: Optional[np.ndarray] = None) -> "ProgressiveFrame":
         """rt_frame_restore: the frame a `ProgressiveFrame.save` blob holds, to be continued on this ctx
-        (which must hold the scene the blob was saved over)."""
-        return restore_frame(self, blob)
+        (which must hold the scene the blob was saved over). With the `ProgressiveFrame.moments()` array
+        taken at that save, the restored frame tracks moments too (rt_frame_restore_ex)."""
+        return restore_frame(self, blob, moments)
 
     def render(self, cam: rt_camera, params: rt_render_params, col_gens: Optional[np.ndarray] = None,
                linear: bool = False, want_gens: bool = False):
@@ -844,4 +864,5 @@ def assemble_host(slabs: np.ndarray, params: rt_render_params) -> np.ndarray:
     return img.reshape(H, W, 3)
 
 
-from .progressive import ProgressiveFrame, blob_info, render_progressive, restore_frame  # noqa: E402
+from .progressive import (ProgressiveFrame, blob_info, error_estimate, render_progressive,  # noqa: E402
+                          restore_frame)

@@ -9,6 +9,10 @@ for bit, whatever the steps.
             rgb, lin, stats = fr.resolve()
 
 `render_progressive` wraps that loop as a generator with the 8-bit stopping rule.
+
+A frame opened with `moments=True` also keeps the second moments of its chunk sums (rt.h, RT_FRAME_MOMENTS):
+`fr.error(abs_tol, rel_tol)` is the per-pixel standard error of the mean and its summary at any point
+after two chunks, and `render_progressive(..., stop_unconverged_fraction=...)` stops on it.
 """
 from __future__ import annotations
 
@@ -27,25 +31,44 @@ PARAM_FIELDS = ("width", "height", "spp", "max_depth", "rng_mode", "flags", "see
                 "shard_count")
 
 
+ERROR_FIELDS = ("chunks_done", "samples_done", "pixels", "nonfinite_pixels", "unconverged_pixels", "max_se", "mean_se")
+
+
 def _stats_dict(s) -> dict:
     return {k: getattr(s, k) for k in STATS_FIELDS}
+
+
+def _error_dict(s) -> dict:
+    return {k: getattr(s, k) for k in ERROR_FIELDS}
+
+
+def _doubles(a, shape=None) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if shape is not None and a.shape != shape:
+        raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
+    return a
 
 
 class ProgressiveFrame:
     """One open frame of a Context (rt_frame_open / rt_frame_restore). Also a context manager."""
 
-    def __init__(self, ctx, handle, params):
+    def __init__(self, ctx, handle, params, tracks_moments: bool = False):
         self._ctx = ctx
         self._h = handle
         self.width, self.height, self.spp = params.width, params.height, params.spp
         self.chunk, self.chunks_total = _rt.frame_chunking(self.width * self.height, self.spp)
         self.chunks_done = 0
+        self.tracks_moments = bool(tracks_moments)
 
     @classmethod
-    def open(cls, ctx, cam, params) -> "ProgressiveFrame":
+    def open(cls, ctx, cam, params, moments: bool = False) -> "ProgressiveFrame":
         h = C.c_void_p()
-        _rt._check(_rt.lib().rt_frame_open(ctx._h, C.byref(cam), C.byref(params), C.byref(h)), "rt_frame_open")
-        return cls(ctx, h, params)
+        if moments:
+            _rt._check(_rt.lib().rt_frame_open_ex(ctx._h, C.byref(cam), C.byref(params), _rt.RT_FRAME_MOMENTS,
+                                                  C.byref(h)), "rt_frame_open_ex")
+        else:
+            _rt._check(_rt.lib().rt_frame_open(ctx._h, C.byref(cam), C.byref(params), C.byref(h)), "rt_frame_open")
+        return cls(ctx, h, params, moments)
 
     @property
     def complete(self) -> bool:
@@ -82,6 +105,25 @@ class ProgressiveFrame:
         _rt._check(_rt.lib().rt_frame_save(self._handle(), buf, n.value, C.byref(n)), "rt_frame_save")
         return buf.raw[:n.value]
 
+    def moments(self) -> np.ndarray:
+        """rt_frame_moments: Q[H,W,3], the second moments of the chunk sums (rt.h), for `restore_frame` and
+        `error_estimate`. RTError (RT_E_STATE) on a frame that does not track them."""
+        q = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        _rt._check(_rt.lib().rt_frame_moments(self._handle(), q.ctypes.data_as(C.POINTER(C.c_double))), "rt_frame_moments")
+        return q
+
+    def error(self, abs_tol: float = 0.0, rel_tol: float = 0.0, want_map: bool = True):
+        """rt_frame_error: (se[H,W,3] | None, stats dict) after at least two chunks: the standard error of
+        each pixel's mean, and pixels / nonfinite_pixels / unconverged_pixels (under abs_tol + rel_tol * |mean|)
+        / max_se / mean_se."""
+        se = np.zeros((self.height, self.width, 3), dtype=np.float64) if want_map else None
+        tol = _rt.rt_error_tol(abs_tol, rel_tol)
+        s = _rt.rt_error_stats()
+        _rt._check(_rt.lib().rt_frame_error(self._handle(), C.byref(tol),
+                                            se.ctypes.data_as(C.POINTER(C.c_double)) if want_map else None,
+                                            C.byref(s)), "rt_frame_error")
+        return se, _error_dict(s)
+
     def close(self):
         # (rt_destroy closes the ctx's open frames itself: after Context.close the handle is dead)
         if self._h is not None and self._ctx._h is not None:
@@ -107,13 +149,37 @@ class ProgressiveFrame:
             pass
 
 
-def restore_frame(ctx, blob: bytes) -> ProgressiveFrame:
+def restore_frame(ctx, blob: bytes, moments: Optional[np.ndarray] = None) -> ProgressiveFrame:
+    """rt_frame_restore, or with `moments` (the saved frame's `moments()` at that save; pairing the two is
+    the caller's business) rt_frame_restore_ex: a tracked frame."""
     info = blob_info(blob)
     h = C.c_void_p()
-    _rt._check(_rt.lib().rt_frame_restore(ctx._h, blob, len(blob), C.byref(h)), "rt_frame_restore")
-    fr = ProgressiveFrame(ctx, h, info["params"])
+    if moments is None:
+        _rt._check(_rt.lib().rt_frame_restore(ctx._h, blob, len(blob), C.byref(h)), "rt_frame_restore")
+    else:
+        q = _doubles(moments, (info["height"], info["width"], 3))
+        _rt._check(_rt.lib().rt_frame_restore_ex(ctx._h, blob, len(blob), q.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 C.byref(h)), "rt_frame_restore_ex")
+    fr = ProgressiveFrame(ctx, h, info["params"], moments is not None)
     fr.chunks_done = info["chunks_done"]
     return fr
+
+
+def error_estimate(sums, moments, chunks_done: int, samples_done: int, abs_tol: float = 0.0, rel_tol: float = 0.0):
+    """rt_error_estimate (host only): (se, stats dict) from image-order sums (a blob's payload) and moments
+    of the same shape [..., 3], by the per-pixel function `ProgressiveFrame.error` runs on the device."""
+    s = _doubles(sums)
+    q = _doubles(moments, s.shape)
+    if s.ndim < 1 or s.shape[-1] != 3:
+        raise ValueError("sums and moments must have 3 channels in their last axis")
+    se = np.zeros_like(s)
+    tol = _rt.rt_error_tol(abs_tol, rel_tol)
+    st = _rt.rt_error_stats()
+    P = C.POINTER(C.c_double)
+    _rt._check(_rt.lib().rt_error_estimate(s.ctypes.data_as(P), q.ctypes.data_as(P), s.size // 3, int(chunks_done),
+                                           int(samples_done), C.byref(tol), se.ctypes.data_as(P), C.byref(st)),
+               "rt_error_estimate")
+    return se, _error_dict(st)
 
 
 def blob_info(blob: bytes) -> dict:
@@ -133,21 +199,35 @@ def blob_info(blob: bytes) -> dict:
 
 
 def render_progressive(ctx, cam, params, step_chunks: int,
-                       stop_changed_fraction: Optional[float] = None) -> Iterator[Tuple[np.ndarray, dict]]:
+                       stop_changed_fraction: Optional[float] = None, *,
+                       stop_unconverged_fraction: Optional[float] = None, abs_tol: float = 0.0,
+                       rel_tol: float = 0.0) -> Iterator[Tuple[np.ndarray, dict]]:
     """Yields (rgb, stats) after each step of `step_chunks` chunks. Stops at completion, or once
     bytes_changed / (3*W*H) of a step is at most `stop_changed_fraction` (the 8-bit stopping rule: the
     bytes stopped moving). `ctx` needs `open_frame(cam, params)` returning a frame with `advance`,
-    `resolve(linear=False)`, `complete` and `close`."""
+    `resolve(linear=False)`, `complete` and `close`.
+
+    With `stop_unconverged_fraction` the frame is opened with `moments=True`, every step that leaves
+    chunks_done >= 2 merges `frame.error(abs_tol, rel_tol, want_map=False)`'s stats into the yielded
+    dict, and the loop also stops once unconverged_pixels <= fraction * (pixels - nonfinite_pixels): the
+    standard error of all but that share of the finite pixels is within abs_tol + rel_tol * |mean|.
+    Either rule stops the loop."""
     if step_chunks < 1:
         raise ValueError("step_chunks must be at least 1")
     channels = 3 * params.width * params.height
-    frame = ctx.open_frame(cam, params)
+    by_error = stop_unconverged_fraction is not None
+    frame = ctx.open_frame(cam, params, moments=True) if by_error else ctx.open_frame(cam, params)
     try:
         while not frame.complete:
             frame.advance(step_chunks)
             rgb, _, stats = frame.resolve(linear=False)
+            met = False
+            if by_error and stats["chunks_done"] >= 2:
+                err = frame.error(abs_tol, rel_tol, want_map=False)[1]
+                stats.update(err)
+                met = err["unconverged_pixels"] <= stop_unconverged_fraction * (err["pixels"] - err["nonfinite_pixels"])
             yield rgb, stats
-            if stop_changed_fraction is not None and stats["bytes_changed"] <= stop_changed_fraction * channels:
+            if met or (stop_changed_fraction is not None and stats["bytes_changed"] <= stop_changed_fraction * channels):
                 break
     finally:
         frame.close()
