@@ -490,7 +490,8 @@ int rt_render_step_profile(rt_ctx* ctx, const rt_camera* cam, const rt_render_pa
 int rt_last_kernel_ms(rt_ctx* ctx, double* out_ms);
 
 /* Which kernel the last tier-B render launch on this ctx ran (kernel selection is per scene and
- * frame: DESIGN.md §3): feature variant (rt_trace.h F_* bits), loop (0 one sample per lane walk,
+ * frame: DESIGN.md §3): feature variant (rt_layout.h F_* bits; 32768: the instantiation an adaptive frame's
+ * launches run, which tests the frame's skip mask), loop (0 one sample per lane walk,
  * 1 ray replacement over the binary tree, 2 over the 4-wide tree), LDS-staged scene or global
  * memory, leaf table in LDS, waves per SIMD the instantiation targets, grid and block size, dynamic
  * LDS bytes per workgroup, work-items and samples per work-item. */
@@ -612,8 +613,52 @@ int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
  *             sequential sum in pixel and channel order. chunks_done < 2, pixels <= 0, samples_done <
  *             chunks_done, a null array or a bad tolerance: RT_E_INVALID.
  *
- * Not covered: sharded or multi-device frames, adaptive sampling, error estimates for tier A, and
- * extending a frame past its spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its per-chunk meaning.
+ *
+ * Adaptive frames: stopping pixels. A frame becomes adaptive through calls (rt_frame_adapt, rt_frame_stop),
+ * not through an open flag; a frame on which neither is made renders exactly as above.
+ *   - Each pixel of a frame is active or stopped. Stopping is permanent.
+ *   - A pixel stopped when the frame had K_p chunks done keeps its S and Q from that moment: the sums of
+ *     chunks 0..K_p-1 of the tier-B definition, bit for bit the values an unadapted frame of the same
+ *     (scene, camera, params) holds after K_p chunks. For an active pixel K_p = chunks_done.
+ *   - N_p = min(spp, K_p * CH). Resolve gives S_p / N_p. rt_frame_error uses (K_p, N_p) per pixel; a pixel
+ *     with K_p < 2 is non-finite (its se channels are NaN).
+ *   - rt_frame_advance renders the next chunks for active pixels only. With no active pixel it renders
+ *     nothing and reports 0 chunks, as on a complete frame (chunks_done stays).
+ *   - The image is a fixed function of (scene, camera, params, and the sequence of stop calls, each with the
+ *     chunks_done it was made at). It does not depend on the step pattern between stop calls, on chunk
+ *     batching, or on other calls interleaved on the ctx.
+ * adapt       Applies a rule on the device to the active pixels at the frame's current (K, N) = (chunks_done,
+ *             samples_done). With RT_ADAPT_NAN a pixel whose S has a NaN channel stops (resolve's nan_pixels:
+ *             such a sum never recovers, its bytes are 0 and its linear value NaN whatever is added, so with
+ *             RT_ADAPT_NAN alone the finished image is rt_render's bit for bit). Otherwise, with
+ *             RT_ADAPT_CONVERGED, a pixel stops when K >= max(2, min_chunks) and it is converged under
+ *             (abs_tol, rel_tol) by rt_frame_error's rule. Pixels with infinite sums never stop. RT_E_INVALID:
+ *             flags 0 or unknown bits, a negative or NaN tolerance, min_chunks < 2 with RT_ADAPT_CONVERGED.
+ *             RT_E_STATE: no chunk rendered yet, a frame whose ctx's scene was replaced, RT_ADAPT_CONVERGED on
+ *             a frame without moments. RT_ADAPT_NAN alone needs only S and works on untracked frames.
+ *             Stopping on an estimated error biases the stopped pixels: the chunks that looked quiet are the
+ *             ones kept (a pixel whose first chunks happen to agree stops on too small an estimate).
+ *             min_chunks is the guard.
+ * stop        The caller's own rule: mask holds H*W bytes in image order, nonzero = stop that pixel now (a
+ *             pixel already stopped stays as it is). Works on untracked frames. RT_E_STATE as for adapt.
+ * adapt stats pixels = H*W; active_pixels; stopped_nan = stopped pixels whose S has a NaN channel;
+ *             stopped_converged_or_masked = the other stopped pixels; stopped_now = this call's. All exact.
+ *             `out` may be NULL.
+ * chunk_counts K_p per pixel, H*W int32 in image order (an active pixel: chunks_done).
+ * save        rt_frame_save on a frame with any stopped pixel returns RT_E_STATE: the version-1 blob has no
+ *             room for K_p and stays as it is. rt_frame_moments still works on an adapted frame.
+ * rt_adapt_decide  The same per-pixel rule on the host alone (no device), over image-order arrays (a blob's
+ *             payload and the saved moments at `chunks_done` chunks of a frame of chunk size `chunk`):
+ *             chunks_out[i] = chunks_in[i] where that is nonzero (already stopped), chunks_done where the
+ *             rule stops pixel i now, else 0 (active). moments may be NULL for a rule without
+ *             RT_ADAPT_CONVERGED; chunks_in may be NULL (no pixel stopped yet); chunks_out may be chunks_in;
+ *             one of chunks_out and out may be NULL. The stats classify stopped pixels by the sums passed.
+ *             RT_E_INVALID: a null sums or rule, a bad rule, pixels < 1, chunks_done outside
+ *             [1, ceil(spp / chunk)], a chunks_in value outside [0, chunks_done].
+ *
+ * Not covered: sharded or multi-device frames, reactivating a stopped pixel, adaptive one-shot rt_render,
+ * saving an adapted frame, error estimates and adaptive sampling for tier A, and extending a frame past its
+ * spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its per-chunk meaning.
  */
 #define RT_FRAME_BLOB_VERSION 1u
 #define RT_FRAME_BLOB_HEADER 288
@@ -668,6 +713,29 @@ int rt_frame_restore_ex(rt_ctx* ctx, const void* buf, size_t len, const double* 
 int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_error_stats* out);
 int rt_error_estimate(const double* sums, const double* moments, int64_t pixels, int chunks_done,
                       int samples_done, const rt_error_tol* tol, double* out_se, rt_error_stats* out);
+#define RT_ADAPT_NAN 1u       /* stop pixels whose running sum has a NaN channel (frame_resolve's nan_pixels) */
+#define RT_ADAPT_CONVERGED 2u /* stop finite pixels converged under (abs_tol, rel_tol), rt_frame_error's rule */
+typedef struct rt_adapt_rule {
+    double abs_tol;
+    double rel_tol;
+    int32_t min_chunks;
+    uint32_t flags;
+} rt_adapt_rule; /* 24 bytes */
+typedef struct rt_adapt_stats {
+    int32_t chunks_done;
+    int32_t _pad;
+    int64_t pixels;
+    int64_t active_pixels;
+    int64_t stopped_nan;
+    int64_t stopped_converged_or_masked;
+    int64_t stopped_now;
+} rt_adapt_stats; /* 48 bytes */
+int rt_frame_adapt(rt_frame* f, const rt_adapt_rule* rule, rt_adapt_stats* out);
+int rt_frame_stop(rt_frame* f, const uint8_t* mask, rt_adapt_stats* out);
+int rt_frame_chunk_counts(rt_frame* f, int32_t* out_chunks);
+int rt_adapt_decide(const double* sums, const double* moments, const int32_t* chunks_in, int64_t pixels,
+                    int chunks_done, int chunk, int spp, const rt_adapt_rule* rule, int32_t* chunks_out,
+                    rt_adapt_stats* out);
 /* The fingerprint rt_upload_scene records for a descriptor (host only; the blob's field at 272). */
 int rt_scene_fingerprint(const rt_scene_desc* desc, uint64_t* out);
 /* The chunking of a tier-B frame of `pixels` pixels at `spp` samples (host only): *out_chunk =

@@ -1,7 +1,8 @@
 // rt_frame_error.cpp — the host half of a progressive frame's error estimate (include/rt.h): the error
 // map and its summary from image-order sums and moments, by the per-pixel function the device runs
-// (rt_error.h). No HIP, no device: it builds for the CPU as is (tests/c/error_estimate_check.c drives
-// it under the sanitizers).
+// (rt_error.h), and an adaptive frame's stop rule over the same arrays (rt_adapt_decide). No HIP, no
+// device: it builds for the CPU as is (tests/c/error_estimate_check.c and tests/c/adapt_decide_check.c
+// drive it under the sanitizers).
 #include <string>
 
 #include "rt.h"
@@ -43,6 +44,49 @@ int rt_error_estimate(const double* sums, const double* moments, int64_t pixels,
   }
   const int64_t finite = pixels - st.nonfinite_pixels;
   st.mean_se = finite ? total / (double)(3 * finite) : 0.0;
+  if (out) *out = st;
+  return RT_OK;
+}
+
+int rt_adapt_decide(const double* sums, const double* moments, const int32_t* chunks_in, int64_t pixels,
+                    int chunks_done, int chunk, int spp, const rt_adapt_rule* rule, int32_t* chunks_out,
+                    rt_adapt_stats* out) {
+  if (!sums || !rule || (!chunks_out && !out) || pixels <= 0 || chunks_done < 1 || chunk < 1 || spp < 1 ||
+      (int64_t)(chunks_done - 1) * chunk >= spp) {
+    rt::set_error("rt_adapt_decide: needs sums, a rule, an output, pixels >= 1 and 1 <= chunks_done <= ceil(spp / chunk)");
+    return RT_E_INVALID;
+  }
+  if (!rt::adapt_rule_ok(rule)) {
+    rt::set_error("rt_adapt_decide: bad rule (flags, a negative or NaN tolerance, or min_chunks < 2 with RT_ADAPT_CONVERGED)");
+    return RT_E_INVALID;
+  }
+  if ((rule->flags & RT_ADAPT_CONVERGED) && !moments) {
+    rt::set_error("rt_adapt_decide: RT_ADAPT_CONVERGED needs the moments");
+    return RT_E_INVALID;
+  }
+  if (chunks_in)
+    for (int64_t i = 0; i < pixels; ++i)
+      if (chunks_in[i] < 0 || chunks_in[i] > chunks_done) {
+        rt::set_error("rt_adapt_decide: chunks_in holds a count outside [0, chunks_done]");
+        return RT_E_INVALID;
+      }
+  const int64_t n64 = (int64_t)chunks_done * chunk;
+  const int samples = (int)(n64 < spp ? n64 : spp);
+  rt_adapt_stats st{};
+  st.chunks_done = chunks_done;
+  st.pixels = pixels;
+  for (int64_t i = 0; i < pixels; ++i) {
+    const double* s = sums + 3 * i;
+    int32_t k = chunks_in ? chunks_in[i] : 0;
+    if (k == 0 && rt::adapt_pixel(s, moments ? moments + 3 * i : nullptr, chunks_done, samples, rule->flags,
+                                  rule->abs_tol, rule->rel_tol, rule->min_chunks) != rt::kAdaptKeep) {
+      k = chunks_done;
+      ++st.stopped_now;
+    }
+    if (k) ++((s[0] != s[0] || s[1] != s[1] || s[2] != s[2]) ? st.stopped_nan : st.stopped_converged_or_masked);
+    if (chunks_out) chunks_out[i] = k;
+  }
+  st.active_pixels = pixels - st.stopped_nan - st.stopped_converged_or_masked;
   if (out) *out = st;
   return RT_OK;
 }

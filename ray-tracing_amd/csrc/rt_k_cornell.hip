@@ -5,7 +5,7 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds) {
-  return pick<kVarCornell>(loop, lds, w, count, leaf_lds);
+const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip) {
+  return pick<kVarCornell>(loop, lds, w, count, leaf_lds, false, skip);
 }
 }  // namespace rt

@@ -4,5 +4,7 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_full(int loop, bool lds, int w, bool count) { return pick_full<kVarFull>(loop, lds, w, count); }
+const void* philox_kernel_full(int loop, bool lds, int w, bool count, bool skip) {
+  return pick_full<kVarFull>(loop, lds, w, count, skip);
+}
 }  // namespace rt

@@ -5,7 +5,7 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count) {
-  return pick_full<kVarFullDark>(loop, lds, w, count);
+const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count, bool skip) {
+  return pick_full<kVarFullDark>(loop, lds, w, count, skip);
 }
 }  // namespace rt

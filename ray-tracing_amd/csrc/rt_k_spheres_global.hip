@@ -5,11 +5,14 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_spheres_global(int w) {
-  constexpr unsigned V = kVarSpheres | F_WIDE;
+template <unsigned V>
+const void* global_kernel(int w) {
   if (w == 2) return (const void*)render_philox2<V, 2>;
   if (w == 4) return (const void*)render_philox2<V, 4>;
   if (w == 1) return (const void*)render_philox2<V, 1>;
   return (const void*)render_philox2<V, 3>;
+}
+const void* philox_kernel_spheres_global(int w, bool skip) {
+  return skip ? global_kernel<kVarSpheres | F_WIDE | F_SKIP>(w) : global_kernel<kVarSpheres | F_WIDE>(w);
 }
 }  // namespace rt

@@ -95,6 +95,11 @@ struct LaunchConst {
                          // their colours stored in tail_buf and summed in sample order by tail_combine
   double* tail_buf;      // [unit][3]
   UDiv div_chunk;        // by chunk
+  // (last again: an adaptive progressive frame's skip bitmask, one 64-bit word per 64 consecutive slab
+  // pixels, bit set = the pixel is stopped (rt.h); null: nothing is skipped. Read by the F_SKIP kernels
+  // only, which such a frame's launches select. Device memory: the host's calls of work_item / work_unit
+  // are the instantiations without the test.)
+  const unsigned long long* skip;
 };
 // (its LDS copy sits at the start of the workgroup's lane-stack memory, 16-byte aligned)
 constexpr int kLcBytes = (int)((sizeof(LaunchConst) + 15) & ~(size_t)15);
@@ -144,10 +149,17 @@ __host__ __device__ __forceinline__ bool work_pixel(const LaunchConst& A, uint32
   return px < A.W && row < A.H;
 }
 
+// A slab pixel's bit in a skip bitmask (LaunchConst::skip; null: never set).
+__host__ __device__ __forceinline__ bool skip_bit(const unsigned long long* skip, uint32_t idx) {
+  return skip && ((skip[idx >> 6] >> (idx & 63u)) & 1ull);
+}
+
 // Tier-B work-item -> (slab pixel, sample chunk). Items run tile by tile, chunk by chunk inside a
 // tile, so a wave's 64 consecutive items are one 8x8 pixel block at one chunk (coherent rays).
-// Returns false for pixels outside the image; else the sample range [s0, s1) and the chunk
-// sum's slot in `partial`.
+// Returns false for pixels outside the image and, under SKIP (the F_SKIP kernels), for the stopped pixels
+// of an adaptive frame (A.skip): such a pixel takes the path a pixel outside the image takes. Else the
+// sample range [s0, s1) and the chunk sum's slot in `partial`.
+template <bool SKIP = false>
 __host__ __device__ __forceinline__ bool work_item(const LaunchConst& A, uint32_t wi, int& px, int& row, int& s0,
                                                    int& s1, long long& slot) {
   const uint32_t tp = (uint32_t)(A.tile * A.tile);
@@ -157,6 +169,9 @@ __host__ __device__ __forceinline__ bool work_item(const LaunchConst& A, uint32_
   const uint32_t k = udiv(rem, A.div_tp);
   const uint32_t idx = lt * tp + (rem - k * tp);
   if (!work_pixel(A, idx, px, row)) return false;
+  if constexpr (SKIP) {
+    if (skip_bit(A.skip, idx)) return false;
+  }
   s0 = (A.chunk_base + (int)k) * A.chunk;
   s1 = A.spp < s0 + A.chunk ? A.spp : s0 + A.chunk;
   slot = (long long)k * A.slab + idx;
@@ -181,13 +196,14 @@ constexpr bool kTail = (F & F_FRAMES) != 0;
 // kTailSlot + its index (its colour goes to tail_buf); false for pixels outside the image and for units
 // past the work-item's last sample.
 constexpr long long kTailSlot = 1ll << 40;
+template <bool SKIP = false>
 __host__ __device__ __forceinline__ bool work_unit(const LaunchConst& A, uint32_t wi, int& px, int& row, int& s0,
                                                    int& s1, long long& slot) {
-  if ((long long)wi < A.tail_start) return work_item(A, wi, px, row, s0, s1, slot);
+  if ((long long)wi < A.tail_start) return work_item<SKIP>(A, wi, px, row, s0, s1, slot);
   const uint32_t u = wi - (uint32_t)A.tail_start;
   const uint32_t q = udiv(u, A.div_chunk);
   const uint32_t k = u - q * (uint32_t)A.chunk;
-  if (!work_item(A, (uint32_t)A.tail_start + q, px, row, s0, s1, slot)) return false;
+  if (!work_item<SKIP>(A, (uint32_t)A.tail_start + q, px, row, s0, s1, slot)) return false;
   s0 += (int)k;
   if (s0 >= s1) return false;
   s1 = s0 + 1;
@@ -323,7 +339,7 @@ __device__ __forceinline__ void philox_loop(const RenderArgs& A, const LaunchCon
         const long long wi = (long long)(base + __popcll(mask & lanes_below));
         if (wi >= L.work_total) {
           done = true;
-        } else if (work_item(L, (uint32_t)wi, px, row, s, s_end, w)) {
+        } else if (work_item<(F & F_SKIP) != 0>(L, (uint32_t)wi, px, row, s, s_end, w)) {
           sum = v3(0, 0, 0);
           path = false;
         } else {
@@ -588,8 +604,8 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
           const long long wi = (long long)(rank < avail ? q_next + rank : base2 + (rank - avail));
           if (wi >= L.work_total) {
             done = true;
-          } else if (kTail<F> ? work_unit(L, (uint32_t)wi, px, row, s, s_end, w)
-                              : work_item(L, (uint32_t)wi, px, row, s, s_end, w)) {
+          } else if (kTail<F> ? work_unit<(F & F_SKIP) != 0>(L, (uint32_t)wi, px, row, s, s_end, w)
+                              : work_item<(F & F_SKIP) != 0>(L, (uint32_t)wi, px, row, s, s_end, w)) {
             sum = v3(0, 0, 0);
           } else {
             w = -1;
@@ -734,29 +750,37 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES)
 
 // The tail's work-items (work_unit): each chunk's sample colours added in sample order from 0, as the
 // lane that renders a whole chunk adds them (end_sample), into the chunk's slot.
-__global__ void __launch_bounds__(256) tail_combine(LaunchConst A) {
+template <bool SKIP>
+__device__ __forceinline__ void tail_body(const LaunchConst& A) {
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= A.items_total - A.tail_start) return;
   int px, row, s0, s1;
   long long slot;
-  if (!work_item(A, (uint32_t)(A.tail_start + j), px, row, s0, s1, slot)) return;
+  if (!work_item<SKIP>(A, (uint32_t)(A.tail_start + j), px, row, s0, s1, slot)) return;
   const double* q = A.tail_buf + j * A.chunk * 3;
   V3 sum = v3(0, 0, 0);
   for (int k = 0; k < s1 - s0; ++k) sum = sum + v3(q[3 * k], q[3 * k + 1], q[3 * k + 2]);
   store_partial(A, slot, sum);
 }
+__global__ void __launch_bounds__(256) tail_combine(LaunchConst A) { tail_body<false>(A); }
+__global__ void __launch_bounds__(256) tail_combine_skip(LaunchConst A) { tail_body<true>(A); }
 
 // Tier B: a slab pixel's chunk sums added in chunk order, then averaged and stored (rt.h); with chunk
 // batches, each batch's chunks are added to the running sum of the batches before it.
 // MOMENTS (a tracked progressive frame, RT_FRAME_MOMENTS): the same additions to the sums, and the chunks'
 // (S_k * S_k) / n_k added in chunk order to the pixel's second moments Q (`moments`, [slab pixel][3]; rt.h),
 // n_k the sample count of the frame's chunk chunk_base + k.
-template <bool MOMENTS>
+// SKIP (an adaptive frame's launches): a stopped pixel's sums and moments stay as they are; its chunk sums
+// were never written.
+template <bool MOMENTS, bool SKIP = false>
 __device__ __forceinline__ void combine_body(const LaunchConst& A, double* moments) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= A.slab) return;
   int px, row;
   if (!work_pixel(A, (uint32_t)idx, px, row)) return;  // outside the image: never assembled
+  if constexpr (SKIP) {
+    if (skip_bit(A.skip, (uint32_t)idx)) return;
+  }
   V3 acc = (A.combine & 1) ? vload(A.acc + idx * 3) : v3(0, 0, 0);
   V3 mom = v3(0, 0, 0);
   if constexpr (MOMENTS) {
@@ -787,6 +811,10 @@ __device__ __forceinline__ void combine_body(const LaunchConst& A, double* momen
 __global__ void __launch_bounds__(256) combine_chunks(LaunchConst A) { combine_body<false>(A, nullptr); }
 __global__ void __launch_bounds__(256) combine_chunks_moments(LaunchConst A, double* moments) {
   combine_body<true>(A, moments);
+}
+__global__ void __launch_bounds__(256) combine_chunks_skip(LaunchConst A) { combine_body<false, true>(A, nullptr); }
+__global__ void __launch_bounds__(256) combine_chunks_moments_skip(LaunchConst A, double* moments) {
+  combine_body<true, true>(A, moments);
 }
 
 // ---------------------------------------------------------------- tier A: the reference's stream
@@ -897,13 +925,22 @@ __device__ __forceinline__ long long frame_slot(long long i, int W, int tile, in
 // counts[0] += pixels whose sum has a NaN channel, counts[1] += bytes that change. One pass; the counts
 // are reduced over each wave with ballots, over the block's 4 waves through LDS, and leave the block as
 // one atomic per counter.
-__global__ void __launch_bounds__(256) frame_resolve(LaunchConst A, int samples, unsigned long long* counts) {
+// ADAPT (an adaptive frame, rt.h): a stopped pixel (kp[slab pixel] = K_p != 0) is averaged over its own
+// N_p = min(spp, K_p * CH) samples (A.spp, A.chunk); an active pixel over `samples`.
+template <bool ADAPT>
+__device__ __forceinline__ void resolve_body(const LaunchConst& A, int samples, unsigned long long* counts,
+                                             const int* kp) {
   __shared__ unsigned wave_nan[4], wave_chg[4];
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   bool nan = false, c0 = false, c1 = false, c2 = false;
   if (i < (long long)A.W * A.H) {
-    const V3 sum = vload(A.acc + frame_slot(i, A.W, A.tile, A.tiles_x) * 3);
+    const long long slot = frame_slot(i, A.W, A.tile, A.tiles_x);
+    const V3 sum = vload(A.acc + slot * 3);
     nan = sum.x != sum.x || sum.y != sum.y || sum.z != sum.z;
+    if constexpr (ADAPT) {
+      const long long n = (long long)kp[slot] * A.chunk;
+      if (n) samples = n < A.spp ? (int)n : A.spp;
+    }
     const V3 avg = divide(sum, (double)samples);
     const uint8_t p0 = A.out_rgb[i * 3 + 0], p1 = A.out_rgb[i * 3 + 1], p2 = A.out_rgb[i * 3 + 2];
     store_pixel(A, i, avg);
@@ -924,6 +961,13 @@ __global__ void __launch_bounds__(256) frame_resolve(LaunchConst A, int samples,
     if (bn) atomicAdd(&counts[0], (unsigned long long)bn);
     if (bc) atomicAdd(&counts[1], (unsigned long long)bc);
   }
+}
+__global__ void __launch_bounds__(256) frame_resolve(LaunchConst A, int samples, unsigned long long* counts) {
+  resolve_body<false>(A, samples, counts, nullptr);
+}
+__global__ void __launch_bounds__(256) frame_resolve_adapt(LaunchConst A, int samples, unsigned long long* counts,
+                                                           const int* kp) {
+  resolve_body<true>(A, samples, counts, kp);
 }
 
 // Saved sums (image order) back into a frame's slab-order running sums: assemble<double>'s inverse at
@@ -947,10 +991,13 @@ __global__ void __launch_bounds__(256) frame_scatter(const double* image, double
 // sum of those se in a fixed order (a pixel's channels in order, a wave's lanes by halving shuffles, the
 // waves in wave order) to block_sums[blockIdx.x]: frame_error_sum adds them, so the total has no
 // floating-point atomic in it and repeats.
-__global__ void __launch_bounds__(256) frame_error(const double* sums, const double* moments, double* out_se, int W,
-                                                   int H, int tile, int tiles_x, int chunks, int samples,
-                                                   double abs_tol, double rel_tol, unsigned long long* acc,
-                                                   double* block_sums) {
+// ADAPT (an adaptive frame, rt.h): a stopped pixel (kp[slab pixel] = K_p != 0) is estimated at its own
+// (K_p, N_p = min(spp, K_p * chunk)); with K_p < 2 it is non-finite, its se channels NaN.
+template <bool ADAPT>
+__device__ __forceinline__ void error_body(const double* sums, const double* moments, double* out_se, int W, int H,
+                                           int tile, int tiles_x, int chunks, int samples, double abs_tol,
+                                           double rel_tol, unsigned long long* acc, double* block_sums,
+                                           const int* kp, int chunk, int spp) {
   __shared__ unsigned wave_bad[4], wave_open[4];
   __shared__ unsigned long long wave_max[4];
   __shared__ double wave_sum[4];
@@ -963,7 +1010,20 @@ __global__ void __launch_bounds__(256) frame_error(const double* sums, const dou
     const double s[3] = {sums[slot], sums[slot + 1], sums[slot + 2]};
     const double q[3] = {moments[slot], moments[slot + 1], moments[slot + 2]};
     double se[3];
-    const int cls = rt::pixel_error(s, q, chunks, samples, abs_tol, rel_tol, se);
+    if constexpr (ADAPT) {
+      const int k = kp[slot / 3];
+      if (k) {
+        const long long n = (long long)k * chunk;
+        chunks = k;
+        samples = n < spp ? (int)n : spp;
+      }
+    }
+    int cls = rt::kPixelNonFinite;
+    if (!ADAPT || chunks >= 2) {
+      cls = rt::pixel_error(s, q, chunks, samples, abs_tol, rel_tol, se);
+    } else {
+      se[0] = se[1] = se[2] = __longlong_as_double(0x7ff8000000000000ll);
+    }
     if (out_se) {
       out_se[i * 3 + 0] = se[0];
       out_se[i * 3 + 1] = se[1];
@@ -1001,6 +1061,86 @@ __global__ void __launch_bounds__(256) frame_error(const double* sums, const dou
     if (m) atomicMax(&acc[2], m);
     block_sums[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
   }
+}
+__global__ void __launch_bounds__(256) frame_error(const double* sums, const double* moments, double* out_se, int W,
+                                                   int H, int tile, int tiles_x, int chunks, int samples,
+                                                   double abs_tol, double rel_tol, unsigned long long* acc,
+                                                   double* block_sums) {
+  error_body<false>(sums, moments, out_se, W, H, tile, tiles_x, chunks, samples, abs_tol, rel_tol, acc, block_sums,
+                    nullptr, 0, 0);
+}
+__global__ void __launch_bounds__(256) frame_error_adapt(const double* sums, const double* moments, double* out_se,
+                                                         int W, int H, int tile, int tiles_x, int chunks, int samples,
+                                                         double abs_tol, double rel_tol, unsigned long long* acc,
+                                                         double* block_sums, const int* kp, int chunk, int spp) {
+  error_body<true>(sums, moments, out_se, W, H, tile, tiles_x, chunks, samples, abs_tol, rel_tol, acc, block_sums, kp,
+                   chunk, spp);
+}
+
+// Adaptive frames (rt.h): stops active pixels, by the rule (RULE: rt::adapt_pixel, the host's text, at the
+// frame's K chunks and N samples) or by the caller's image-order byte mask. One thread per slab pixel, so
+// that a wave is one word of the skip bitmask (64 consecutive slab pixels, one 8x8 block; work_pixel is
+// frame_slot's inverse): a newly stopped pixel gets kp = K, and the wave's lane 0 writes the word from one
+// ballot of "stopped before or now" (padding pixels outside the image: never set, never counted).
+// counts[0] += pixels stopped by this call, counts[1] += those of them whose sum has a NaN channel, reduced
+// as frame_resolve reduces its counts.
+template <bool RULE>
+__device__ __forceinline__ void adapt_body(const LaunchConst& A, const double* moments, int* kp,
+                                           unsigned long long* skip, const uint8_t* mask, int K, int N,
+                                           rt_adapt_rule rule, unsigned long long* counts) {
+  __shared__ unsigned wave_now[4], wave_nan[4];
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool stopped = false, now = false, now_nan = false;
+  int px, row;
+  if (idx < A.slab && work_pixel(A, (uint32_t)idx, px, row)) {
+    stopped = kp[idx] != 0;
+    if (!stopped) {
+      const double s[3] = {A.acc[idx * 3], A.acc[idx * 3 + 1], A.acc[idx * 3 + 2]};
+      if constexpr (RULE) {
+        double q[3] = {0.0, 0.0, 0.0};
+        if (moments) q[0] = moments[idx * 3], q[1] = moments[idx * 3 + 1], q[2] = moments[idx * 3 + 2];
+        now = rt::adapt_pixel(s, q, K, N, rule.flags, rule.abs_tol, rule.rel_tol, rule.min_chunks) != rt::kAdaptKeep;
+      } else {
+        now = mask[(long long)row * A.W + px] != 0;
+      }
+      if (now) {
+        kp[idx] = K;
+        now_nan = s[0] != s[0] || s[1] != s[1] || s[2] != s[2];
+      }
+    }
+  }
+  const unsigned long long word = __ballot(stopped || now);
+  const unsigned n_now = (unsigned)__popcll(__ballot(now)), n_nan = (unsigned)__popcll(__ballot(now_nan));
+  if ((threadIdx.x & 63) == 0) {
+    if (idx < A.slab) skip[idx >> 6] = word;  // (the slab is whole 8x8 blocks: a wave is inside it or past it)
+    wave_now[threadIdx.x >> 6] = n_now;
+    wave_nan[threadIdx.x >> 6] = n_nan;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned bn = wave_now[0] + wave_now[1] + wave_now[2] + wave_now[3];
+    const unsigned bq = wave_nan[0] + wave_nan[1] + wave_nan[2] + wave_nan[3];
+    if (bn) atomicAdd(&counts[0], (unsigned long long)bn);
+    if (bq) atomicAdd(&counts[1], (unsigned long long)bq);
+  }
+}
+__global__ void __launch_bounds__(256) frame_adapt(LaunchConst A, const double* moments, int* kp,
+                                                   unsigned long long* skip, int K, int N, rt_adapt_rule rule,
+                                                   unsigned long long* counts) {
+  adapt_body<true>(A, moments, kp, skip, nullptr, K, N, rule, counts);
+}
+__global__ void __launch_bounds__(256) frame_stop_mask(LaunchConst A, int* kp, unsigned long long* skip,
+                                                       const uint8_t* mask, int K, unsigned long long* counts) {
+  adapt_body<false>(A, nullptr, kp, skip, mask, K, 0, rt_adapt_rule{}, counts);
+}
+
+// K_p in image order (rt_frame_chunk_counts): a stopped pixel's kp, else the frame's K.
+__global__ void __launch_bounds__(256) frame_chunk_counts(const int* kp, int* out, int W, int H, int tile,
+                                                          int tiles_x, int K) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)W * H) return;
+  const int k = kp[frame_slot(i, W, tile, tiles_x)];
+  out[i] = k ? k : K;
 }
 
 // frame_error's block sums added in a fixed order by one block: thread t adds blocks t, t + 256, ... in
@@ -1157,10 +1297,11 @@ __global__ void math_probe(int op, const double* x, const double* y, int n, doub
 
 // Kernel pointer for (variant, loop, LDS-staged?, waves per SIMD, counting build?); loop 0 = one
 // sample per lane walk, 1 = ray replacement over the binary tree, 2 = replacement over the
-// 4-wide tree.
+// 4-wide tree. `skip`: the F_SKIP instantiation of the same kernel (an adaptive frame's launches; there
+// is no counting build of those).
 template <unsigned V>
 const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false) {
-  if constexpr (V == (kVarSpheres | F_WIDE)) {
+  if constexpr ((V & ~F_SKIP) == (kVarSpheres | F_WIDE)) {
     if (!lds && q) {  // (the quantised tree and sphere quadruples from global memory)
       if (w == 2) return (const void*)render_philox2<V | F_QNODE, 2>;
       if (w == 3) return (const void*)render_philox2<V | F_QNODE, 3>;
@@ -1187,13 +1328,16 @@ const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false) {
   return (const void*)render_philox2<V, 1>;
 }
 template <unsigned V>
-const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = false) {
-  if (count) {
-    if constexpr (V == kVarSpheres) {
-      if (loop == 2 && q) return (const void*)render_philox2<V | F_WIDE | F_COUNT | F_QNODE, 1>;
+const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = false, bool skip = false) {
+  if constexpr ((V & F_SKIP) == 0) {
+    if (skip) return count ? nullptr : pick<V | F_SKIP>(loop, lds, w, false, leaf_lds, q);
+    if (count) {
+      if constexpr (V == kVarSpheres) {
+        if (loop == 2 && q) return (const void*)render_philox2<V | F_WIDE | F_COUNT | F_QNODE, 1>;
+      }
+      if (loop == 2) return (const void*)render_philox2<V | F_WIDE | F_COUNT, 1>;
+      return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
     }
-    if (loop == 2) return (const void*)render_philox2<V | F_WIDE | F_COUNT, 1>;
-    return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
   }
   if (loop == 2) return pick_w<V | F_WIDE>(lds, w, leaf_lds, q);
   if (loop == 1) return pick_w<V>(lds, w);
@@ -1211,8 +1355,11 @@ const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = 
 // full variants (media, frames, textures, motion): ray replacement over the caller's tree in the
 // reference's order (loop 1), or the per-sample loop (loop 0)
 template <unsigned V>
-const void* pick_full(int loop, bool lds, int w, bool count) {
-  if (count) return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
+const void* pick_full(int loop, bool lds, int w, bool count, bool skip = false) {
+  if constexpr ((V & F_SKIP) == 0) {
+    if (skip) return count ? nullptr : pick_full<V | F_SKIP>(loop, lds, w, false);
+    if (count) return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
+  }
   if (loop) {
     if (lds) return w >= 3 ? (const void*)render_philox2_lds<V, 3> : (const void*)render_philox2_lds<V, 2>;
     if (w >= 4) return (const void*)render_philox2<V, 4>;  // (RTAMD_WAVES=4: A/B only)
@@ -1226,9 +1373,9 @@ const void* pick_full(int loop, bool lds, int w, bool count) {
 // Render-kernel tables, one per kernel translation unit: the kernel for (loop, LDS-staged?, waves per
 // SIMD, counting build?, leaf table in LDS?) of that unit's variant(s).
 namespace rt {
-const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q);
-const void* philox_kernel_spheres_global(int w);  // rt_k_spheres_global.hip
-const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds);
-const void* philox_kernel_full(int loop, bool lds, int w, bool count);
-const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count);
+const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q, bool skip);
+const void* philox_kernel_spheres_global(int w, bool skip);  // rt_k_spheres_global.hip
+const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip);
+const void* philox_kernel_full(int loop, bool lds, int w, bool count, bool skip);
+const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count, bool skip);
 }  // namespace rt

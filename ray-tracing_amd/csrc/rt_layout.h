@@ -67,6 +67,9 @@ enum : unsigned {
   F_QNODE = 4096u, // (spheres-only F_WIDE kernels reading the tree from global memory) the quantised 4-wide
                    // nodes (rt_qnode) and the leaves' sphere quadruples instead of the 128 / 64-byte records
   // (8192 and 16384 stay unused: kernel symbol names carry the flag word)
+  F_SKIP = 32768u, // an adaptive progressive frame's launches: work_item tests the frame's skip bitmask
+                   // (LaunchConst::skip). Its own instantiations, so that every other launch runs the
+                   // kernels without the test
 };
 
 // Kernel variants: spheres-only (configs 1, 2, 5), Cornell-like (rects, instances, lights), full.

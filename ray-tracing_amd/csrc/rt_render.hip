@@ -122,6 +122,15 @@ struct rt_frame {
   double* d_q = nullptr;
   double* d_se = nullptr;
   unsigned long long* d_err = nullptr;
+  // Adaptive frames (rt.h), all allocated by the first stop call: K_p per slab pixel (0 = active), the skip
+  // bitmask the render kernels read (one 64-bit word per 64 consecutive slab pixels), frame_adapt's
+  // {stopped now, of them NaN}, and on first use the image-order staging of a caller's mask / of K_p
+  int* d_kp = nullptr;
+  unsigned long long* d_skip = nullptr;
+  unsigned long long* d_adapt = nullptr;
+  uint8_t* d_mask = nullptr;
+  int* d_kimg = nullptr;
+  long long stopped_nan = 0, stopped_other = 0;  // stopped pixels by their sums (rt_adapt_stats)
   rt_frame_stats last{};     // the last resolve's counts (a poll with nothing new rendered repeats them)
   // one event pair per advance since the last resolve (kernel_ms); `used` of them are pending
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -138,6 +147,7 @@ struct ChunkSpan {
   bool keep = false;        // keep the running sums in `acc` after the last chunk (no image is stored)
   double* moments = nullptr;  // a tracked frame's second moments, folded with the sums (combine_chunks_moments)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;  // around the render launches; nullptr: the ctx's ev0 / ev1
+  const unsigned long long* skip = nullptr;  // an adaptive frame's skip bitmask (LaunchConst::skip)
 };
 
 namespace {
@@ -307,15 +317,17 @@ int waves_target(int dflt) {
   return (w >= 1 && w <= 4) ? w : dflt;
 }
 // (the render kernels live in one translation unit per variant: rt_k_*.hip)
-const void* philox_kernel(unsigned var, int loop, bool lds, int w, bool count, bool leaf_lds = false, bool q = false) {
+// (skip: the F_SKIP instantiation, an adaptive frame's launches)
+const void* philox_kernel(unsigned var, int loop, bool lds, int w, bool count, bool skip, bool leaf_lds = false,
+                          bool q = false) {
   if (var == kVarSpheres) {
     // (the 4-wide tree from global memory, 128-byte nodes: its own unit, rt_k_spheres_global.hip)
-    if (loop == 2 && !lds && !count && !q && !std::getenv("RTAMD_NO_COLD")) return rt::philox_kernel_spheres_global(w);
-    return rt::philox_kernel_spheres(loop, lds, w, count, leaf_lds, q);
+    if (loop == 2 && !lds && !count && !q && !std::getenv("RTAMD_NO_COLD")) return rt::philox_kernel_spheres_global(w, skip);
+    return rt::philox_kernel_spheres(loop, lds, w, count, leaf_lds, q, skip);
   }
-  if (var == kVarCornell) return rt::philox_kernel_cornell(loop, lds, w, count, leaf_lds);
-  if (var == kVarFullDark) return rt::philox_kernel_full_dark(loop, lds, w, count);
-  return rt::philox_kernel_full(loop, lds, w, count);
+  if (var == kVarCornell) return rt::philox_kernel_cornell(loop, lds, w, count, leaf_lds, skip);
+  if (var == kVarFullDark) return rt::philox_kernel_full_dark(loop, lds, w, count, skip);
+  return rt::philox_kernel_full(loop, lds, w, count, skip);
 }
 bool env_off(const char* name) {
   const char* e = std::getenv(name);
@@ -356,7 +368,9 @@ int exact_launch(rt_ctx* c, bool shared_libm, const void** fn, size_t* bytes) {
 int launch_combine(rt_ctx* c, const LaunchConst& A, hipStream_t st, double* moments) {
   LaunchConst B = A;
   void* args[] = {&B, &moments};  // (combine_chunks takes the first alone)
-  const void* fn = moments ? (const void*)combine_chunks_moments : (const void*)combine_chunks;
+  // (an adaptive frame's launch, A.skip: the bodies that leave stopped pixels alone)
+  const void* fn = A.skip ? (moments ? (const void*)combine_chunks_moments_skip : (const void*)combine_chunks_skip)
+                          : (moments ? (const void*)combine_chunks_moments : (const void*)combine_chunks);
   HIPCHK(hipLaunchKernel(fn, dim3((unsigned)((A.slab + 255) / 256)), dim3(256), args, 0, st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_done, st));
@@ -420,6 +434,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   A.prof = d_prof;
   A.out_rgb = d_rgb;
   A.out_lin = d_lin;
+  A.skip = span.skip;
   // The work counter and the chunk-sum buffer are the ctx's: order this launch after the previous
   // one, whichever stream that was on (on the same stream, stream order already does).
   if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
@@ -520,7 +535,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
       if (A.tail_start < A.items_total) {
         LaunchConst B = A;
         void* targs[] = {&B};
-        HIPCHK(hipLaunchKernel((const void*)tail_combine, dim3((unsigned)((A.items_total - A.tail_start + 255) / 256)),
+        HIPCHK(hipLaunchKernel(A.skip ? (const void*)tail_combine_skip : (const void*)tail_combine, dim3((unsigned)((A.items_total - A.tail_start + 255) / 256)),
                                dim3(256), targs, 0, st));
         HIPCHK(hipGetLastError());
       }
@@ -575,6 +590,8 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   A.rev_tiles = env_off("RTAMD_TILE_REV") || !std::getenv("RTAMD_TILE_REV") ? 0u : (uint32_t)per_shard;
   const unsigned var = variant_for(c->features);
   const bool count = d_work != nullptr;
+  const bool skip = A.skip != nullptr;  // (an adaptive frame: the F_SKIP kernels, which test its mask)
+  if (skip && count) return invalid("the counting build has no adaptive-frame kernels");
   // Replacement loop (RTAMD_REPLACE=0 disables) for every world whose instance frames nest at most
   // RT_MAX_FRAMES deep; worlds with media or frames walk the caller's tree in the reference's order.
   // Over the 4-wide tree when one was built (RTAMD_WIDE=0 disables; the reference-cull flag asks
@@ -622,11 +639,11 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
     const int block = waves * 256;
     const size_t bytes = lds_bytes(waves, n_leaves);
     if (bytes <= kLdsBudget) {
-      const void* fn = philox_kernel(var, loop, true, waves, false, n_leaves > 0);
+      const void* fn = philox_kernel(var, loop, true, waves, false, skip, n_leaves > 0);
       HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
       int n_items = items;
       void* args[] = {&R, &n_items, (void*)&entries, &n_leaves};
-      c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u), loop, 1, n_leaves > 0, waves, c->cu_count,
+      c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (skip ? F_SKIP : 0u), loop, 1, n_leaves > 0, waves, c->cu_count,
                                       block, (int)bytes, A.work_total, A.chunk,
                                       (loop == 2 || (loop == 1 && c->mixed_wide)) ? c->n_wnodes : 0, batches, 0};
       return run(fn, dim3(c->cu_count), dim3(block), bytes, args);
@@ -634,7 +651,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   }
   // (spheres-only worlds uploaded with RTAMD_QNODE=1 read the 4-wide tree from global memory in its
   // 64-byte quantised form: A/B only, measured slower)
-  const void* fn = philox_kernel(var, loop, false, count ? 1 : waves, count, false, loop == 2 && c->d_qnodes);
+  const void* fn = philox_kernel(var, loop, false, count ? 1 : waves, count, skip, false, loop == 2 && c->d_qnodes);
   // replacement loops: lane stacks (+ Side slots) in dynamic LDS, sized for this world's stack bound
   // (wide_node writes 3 slots)
   int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;
@@ -646,7 +663,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   const long long want = (A.work_total + RT_BLOCK - 1) / RT_BLOCK;
   const long long resident = (long long)c->cu_count * std::max(1, bpc);
   const int grid = (int)std::max(1ll, std::min(want, resident));
-  c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (count ? F_COUNT : 0u), loop, 0, 0,
+  c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (count ? F_COUNT : 0u) | (skip ? F_SKIP : 0u), loop, 0, 0,
                                   count ? 1 : waves, grid, RT_BLOCK, (int)dyn, A.work_total, A.chunk,
                                   (loop == 2 || (loop == 1 && c->mixed_wide)) ? c->n_wnodes : 0, batches, 0};
   void* args[] = {&R, &entries};
@@ -1245,6 +1262,11 @@ void frame_free(rt_frame* f) {
   (void)hipFree(f->d_q);
   (void)hipFree(f->d_se);
   (void)hipFree(f->d_err);
+  (void)hipFree(f->d_kp);
+  (void)hipFree(f->d_skip);
+  (void)hipFree(f->d_adapt);
+  (void)hipFree(f->d_mask);
+  (void)hipFree(f->d_kimg);
   for (auto& e : f->events) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
@@ -1303,6 +1325,62 @@ int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, uint
   return RT_OK;
 }
 
+// One stop call of an adaptive frame (rt_frame_adapt: `rule`; rt_frame_stop: the caller's `mask`, image
+// order): the first one allocates K_p and the skip bitmask (zeroed: every pixel active), the kernel stops
+// pixels at the frame's current chunks_done, and the host keeps the exact totals.
+int frame_stop_call(rt_frame* f, const rt_adapt_rule* rule, const uint8_t* mask, const char* what,
+                    rt_adapt_stats* out) {
+  int rc = frame_live(f, what);
+  if (rc) return rc;
+  if (f->chunks_done == 0) return state_error(std::string(what) + ": no chunk rendered yet");
+  if (rule && (rule->flags & RT_ADAPT_CONVERGED) && !f->d_q)
+    return state_error(std::string(what) + ": RT_ADAPT_CONVERGED needs a frame opened with RT_FRAME_MOMENTS");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  const size_t words = (size_t)(f->slab / 64);  // (the slab is whole 8x8 blocks)
+  if (!f->d_skip) {  // (the mask last: advance, resolve and error take the adaptive path once it is there)
+    if (!f->d_adapt) HIPCHK(hipMalloc((void**)&f->d_adapt, 2 * sizeof(unsigned long long)));
+    if (!f->d_kp) HIPCHK(hipMalloc((void**)&f->d_kp, sizeof(int) * (size_t)f->slab));
+    HIPCHK(hipMemsetAsync(f->d_kp, 0, sizeof(int) * (size_t)f->slab, c->stream));
+    HIPCHK(hipMalloc((void**)&f->d_skip, sizeof(unsigned long long) * words));
+    HIPCHK(hipMemsetAsync(f->d_skip, 0, sizeof(unsigned long long) * words, c->stream));
+  }
+  LaunchConst A{};
+  long long per_shard;
+  fill_frame_geometry(A, &f->p, 0, 1, per_shard);
+  A.acc = f->d_sum;
+  int K = f->chunks_done, N = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
+  unsigned long long* d_counts = f->d_adapt;
+  HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+  const dim3 grid((unsigned)((f->slab + 255) / 256));
+  if (rule) {
+    hipLaunchKernelGGL(frame_adapt, grid, dim3(256), 0, c->stream, A, (const double*)f->d_q, f->d_kp, f->d_skip, K, N,
+                       *rule, d_counts);
+  } else {
+    if (!f->d_mask) HIPCHK(hipMalloc((void**)&f->d_mask, (size_t)f->npx));
+    HIPCHK(hipMemcpyAsync(f->d_mask, mask, (size_t)f->npx, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(frame_stop_mask, grid, dim3(256), 0, c->stream, A, f->d_kp, f->d_skip,
+                       (const uint8_t*)f->d_mask, K, d_counts);
+  }
+  HIPCHK(hipGetLastError());
+  unsigned long long counts[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  f->stopped_nan += (long long)counts[1];
+  f->stopped_other += (long long)(counts[0] - counts[1]);
+  if (out) {
+    rt_adapt_stats st{};
+    st.chunks_done = f->chunks_done;
+    st.pixels = (int64_t)f->npx;
+    st.stopped_nan = f->stopped_nan;
+    st.stopped_converged_or_masked = f->stopped_other;
+    st.active_pixels = st.pixels - st.stopped_nan - st.stopped_converged_or_masked;
+    st.stopped_now = (int64_t)counts[0];
+    *out = st;
+  }
+  return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1326,6 +1404,7 @@ int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
   if (max_chunks < 0) return invalid("rt_frame_advance: max_chunks must not be negative");
   const int n = std::min(max_chunks, f->chunks_total - f->chunks_done);
   if (n == 0) return RT_OK;  // (a complete frame: nothing left to render)
+  if (f->stopped_nan + f->stopped_other == f->npx) return RT_OK;  // (an adaptive frame with no active pixel)
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
   if (f->used == f->events.size()) {
@@ -1343,6 +1422,7 @@ int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
   span.acc = f->d_sum;
   span.keep = true;
   span.moments = f->d_q;
+  span.skip = f->d_skip;
   span.ev_begin = f->events[f->used].first;
   span.ev_end = f->events[f->used].second;
   rc = launch_philox(c, &f->cam, &f->p, 0, 1, nullptr, nullptr, c->stream, nullptr, nullptr, span);
@@ -1375,8 +1455,12 @@ int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb, double* out_lin, rt_frame_st
     int samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
     unsigned long long* d_counts = f->d_counts;
     HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    void* args[] = {&A, &samples, &d_counts};
-    HIPCHK(hipLaunchKernel((const void*)frame_resolve, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), args, 0,
+    // (an adapted frame: each stopped pixel over its own N_p = min(spp, K_p * CH))
+    A.spp = f->p.spp;
+    A.chunk = f->chunk;
+    const int* d_kp = f->d_kp;
+    void* args[] = {&A, &samples, &d_counts, &d_kp};  // (frame_resolve takes the first three)
+    HIPCHK(hipLaunchKernel(d_kp ? (const void*)frame_resolve_adapt : (const void*)frame_resolve, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), args, 0,
                            c->stream));
     HIPCHK(hipGetLastError());
     unsigned long long counts[2] = {0, 0};  // (copied in stream order: one wait for the kernel and the counts)
@@ -1404,6 +1488,8 @@ int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb, double* out_lin, rt_frame_st
 int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len) {
   int rc = frame_live(f, "rt_frame_save");
   if (rc) return rc;
+  if (f->stopped_nan + f->stopped_other > 0)
+    return state_error("rt_frame_save: the frame has stopped pixels (the version-1 blob has no room for their chunk counts)");
   const size_t payload = sizeof(double) * 3 * (size_t)f->npx;
   const size_t need = RT_FRAME_BLOB_HEADER + payload;
   if (out_len) *out_len = need;
@@ -1520,8 +1606,13 @@ int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_erro
   unsigned long long* d_acc = f->d_err;
   double *d_block = reinterpret_cast<double*>(f->d_err + 4), *d_total = reinterpret_cast<double*>(f->d_err + 3);
   HIPCHK(hipMemsetAsync(d_acc, 0, 4 * sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(frame_error, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_sum, d_q, d_se, W, H, tile, tiles_x,
-                     chunks, samples, abs_tol, rel_tol, d_acc, d_block);
+  if (f->d_kp)  // (an adapted frame: each stopped pixel at its own (K_p, N_p))
+    hipLaunchKernelGGL(frame_error_adapt, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_sum, d_q, d_se, W, H, tile,
+                       tiles_x, chunks, samples, abs_tol, rel_tol, d_acc, d_block, (const int*)f->d_kp, f->chunk,
+                       f->p.spp);
+  else
+    hipLaunchKernelGGL(frame_error, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_sum, d_q, d_se, W, H, tile,
+                       tiles_x, chunks, samples, abs_tol, rel_tol, d_acc, d_block);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(frame_error_sum, dim3(1), dim3(256), 0, c->stream, (const double*)d_block, blocks, d_total);
   HIPCHK(hipGetLastError());
@@ -1543,6 +1634,41 @@ int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_erro
     st.mean_se = finite ? total / (double)(3 * finite) : 0.0;
     *out = st;
   }
+  return RT_OK;
+}
+
+int rt_frame_adapt(rt_frame* f, const rt_adapt_rule* rule, rt_adapt_stats* out) {
+  if (!f) return invalid("rt_frame_adapt: null frame");
+  if (!rt::adapt_rule_ok(rule))
+    return invalid("rt_frame_adapt: bad rule (null, flags 0 or unknown, a negative or NaN tolerance, or min_chunks < 2 "
+                   "with RT_ADAPT_CONVERGED)");
+  return frame_stop_call(f, rule, nullptr, "rt_frame_adapt", out);
+}
+
+int rt_frame_stop(rt_frame* f, const uint8_t* mask, rt_adapt_stats* out) {
+  if (!f || !mask) return invalid("rt_frame_stop: null argument");
+  return frame_stop_call(f, nullptr, mask, "rt_frame_stop", out);
+}
+
+int rt_frame_chunk_counts(rt_frame* f, int32_t* out_chunks) {
+  int rc = frame_live(f, "rt_frame_chunk_counts");
+  if (rc) return rc;
+  if (!out_chunks) return invalid("rt_frame_chunk_counts: null argument");
+  if (!f->d_kp) {  // (no stop call yet: every pixel is active)
+    std::fill(out_chunks, out_chunks + f->npx, (int32_t)f->chunks_done);
+    return RT_OK;
+  }
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  if (!f->d_kimg) HIPCHK(hipMalloc((void**)&f->d_kimg, sizeof(int) * (size_t)f->npx));
+  int tile, tiles_x;
+  long long tt, ps, slab;
+  geometry(&f->p, tile, tiles_x, tt, ps, slab);
+  hipLaunchKernelGGL(frame_chunk_counts, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
+                     (const int*)f->d_kp, f->d_kimg, f->p.width, f->p.height, tile, tiles_x, f->chunks_done);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(out_chunks, f->d_kimg, sizeof(int) * (size_t)f->npx, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

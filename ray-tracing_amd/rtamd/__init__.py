@@ -34,6 +34,8 @@ RT_FLAG_REFERENCE_CULL = 2
 RT_FLAG_NAN_ZERO = 4  # parity diagnostic: NaN sample channels add 0 (rt.h)
 RT_FLAG_SHARED_LIBM = 8  # tier A parity aid: the portable include/rt_libm.h transcendentals on both sides
 RT_UPLOAD_REFERENCE_BVH = 1
+RT_ADAPT_NAN = 1        # rt_frame_adapt: stop pixels whose running sum has a NaN channel
+RT_ADAPT_CONVERGED = 2  # ... and finite pixels converged under (abs_tol, rel_tol)
 RT_FRAME_MOMENTS = 1  # rt_frame_open_ex: keep the chunk sums' second moments (per-pixel error estimates)
 RT_DEBUG_RESUMABLE = 4  # rt_debug_closest_hits: the render loop's resumable binary walk
 RT_DEBUG_WIDE = 8       # rt_debug_closest_hits: the resumable walk over the 4-wide fp32-box tree
@@ -147,7 +149,19 @@ class rt_error_stats(C.Structure):
 
 
 assert C.sizeof(rt_frame_stats) == 40 and C.sizeof(rt_frame_blob_desc) == 288
+
+
+class rt_adapt_rule(C.Structure):
+    _fields_ = [("abs_tol", C.c_double), ("rel_tol", C.c_double), ("min_chunks", C.c_int32), ("flags", C.c_uint32)]
+
+
+class rt_adapt_stats(C.Structure):
+    _fields_ = [("chunks_done", C.c_int32), ("_pad", C.c_int32), ("pixels", C.c_int64), ("active_pixels", C.c_int64),
+                ("stopped_nan", C.c_int64), ("stopped_converged_or_masked", C.c_int64), ("stopped_now", C.c_int64)]
+
+
 assert C.sizeof(rt_error_tol) == 16 and C.sizeof(rt_error_stats) == 48
+assert C.sizeof(rt_adapt_rule) == 24 and C.sizeof(rt_adapt_stats) == 48
 assert C.sizeof(rt_node) == 64 and C.sizeof(rt_material) == 16 and C.sizeof(rt_texture) == 48
 assert C.sizeof(rt_perlin) == 9216 and C.sizeof(rt_camera) == 192 and C.sizeof(rt_render_params) == 48
 assert C.sizeof(rt_scene_desc) == 112
@@ -169,6 +183,7 @@ EXPORTED = [
     "rt_frame_open", "rt_frame_advance", "rt_frame_resolve", "rt_frame_save", "rt_frame_restore",
     "rt_frame_blob_info", "rt_frame_close", "rt_scene_fingerprint", "rt_frame_chunking",
     "rt_frame_open_ex", "rt_frame_moments", "rt_frame_restore_ex", "rt_frame_error", "rt_error_estimate",
+    "rt_frame_adapt", "rt_frame_stop", "rt_frame_chunk_counts", "rt_adapt_decide",
 ]
 
 # include/rt_wide.h: one 4-wide node (128 B)
@@ -271,6 +286,11 @@ def lib() -> C.CDLL:
             "rt_frame_restore_ex": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(D), P(C.c_void_p)]),
             "rt_frame_error": (I, [C.c_void_p, P(rt_error_tol), P(D), P(rt_error_stats)]),
             "rt_error_estimate": (I, [P(D), P(D), C.c_int64, I, I, P(rt_error_tol), P(D), P(rt_error_stats)]),
+            "rt_frame_adapt": (I, [C.c_void_p, P(rt_adapt_rule), P(rt_adapt_stats)]),
+            "rt_frame_stop": (I, [C.c_void_p, P(C.c_uint8), P(rt_adapt_stats)]),
+            "rt_frame_chunk_counts": (I, [C.c_void_p, P(C.c_int32)]),
+            "rt_adapt_decide": (I, [P(D), P(D), P(C.c_int32), C.c_int64, I, I, I, P(rt_adapt_rule), P(C.c_int32),
+                                    P(rt_adapt_stats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -864,5 +884,5 @@ def assemble_host(slabs: np.ndarray, params: rt_render_params) -> np.ndarray:
     return img.reshape(H, W, 3)
 
 
-from .progressive import (ProgressiveFrame, blob_info, error_estimate, render_progressive,  # noqa: E402
-                          restore_frame)
+from .progressive import (ProgressiveFrame, adapt_decide, blob_info, error_estimate,  # noqa: E402
+                          render_progressive, restore_frame)

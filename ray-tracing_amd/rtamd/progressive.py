@@ -13,6 +13,10 @@ for bit, whatever the steps.
 A frame opened with `moments=True` also keeps the second moments of its chunk sums (rt.h, RT_FRAME_MOMENTS):
 `fr.error(abs_tol, rel_tol)` is the per-pixel standard error of the mean and its summary at any point
 after two chunks, and `render_progressive(..., stop_unconverged_fraction=...)` stops on it.
+
+Adaptive frames (rt.h): `fr.adapt(...)` stops the pixels whose sum is NaN (nothing is lost: their bytes stay 0)
+and those already converged under a tolerance, `fr.stop(mask)` the caller's own choice; later `advance` calls
+render the active pixels only. `render_progressive(..., adaptive=True)` calls `adapt` after every step.
 """
 from __future__ import annotations
 
@@ -31,6 +35,7 @@ PARAM_FIELDS = ("width", "height", "spp", "max_depth", "rng_mode", "flags", "see
                 "shard_count")
 
 
+ADAPT_FIELDS = ("chunks_done", "pixels", "active_pixels", "stopped_nan", "stopped_converged_or_masked", "stopped_now")
 ERROR_FIELDS = ("chunks_done", "samples_done", "pixels", "nonfinite_pixels", "unconverged_pixels", "max_se", "mean_se")
 
 
@@ -40,6 +45,15 @@ def _stats_dict(s) -> dict:
 
 def _error_dict(s) -> dict:
     return {k: getattr(s, k) for k in ERROR_FIELDS}
+
+
+def _adapt_dict(s) -> dict:
+    return {k: getattr(s, k) for k in ADAPT_FIELDS}
+
+
+def _adapt_rule(abs_tol, rel_tol, min_chunks, nan, converged):
+    flags = (_rt.RT_ADAPT_NAN if nan else 0) | (_rt.RT_ADAPT_CONVERGED if converged else 0)
+    return _rt.rt_adapt_rule(abs_tol, rel_tol, int(min_chunks), flags)
 
 
 def _doubles(a, shape=None) -> np.ndarray:
@@ -59,6 +73,7 @@ class ProgressiveFrame:
         self.chunk, self.chunks_total = _rt.frame_chunking(self.width * self.height, self.spp)
         self.chunks_done = 0
         self.tracks_moments = bool(tracks_moments)
+        self.active_pixels = self.width * self.height  # (pixels no stop call has stopped)
 
     @classmethod
     def open(cls, ctx, cam, params, moments: bool = False) -> "ProgressiveFrame":
@@ -124,6 +139,37 @@ class ProgressiveFrame:
                                             C.byref(s)), "rt_frame_error")
         return se, _error_dict(s)
 
+    def adapt(self, abs_tol: float = 0.0, rel_tol: float = 0.0, min_chunks: int = 2, nan: bool = True,
+              converged: bool = True) -> dict:
+        """rt_frame_adapt: stops, for good, the active pixels whose running sum has a NaN channel (`nan`) and
+        those with chunks_done >= max(2, min_chunks) that `error`'s rule calls converged under (abs_tol,
+        rel_tol) (`converged`; needs a frame opened with moments). Returns the stats dict: pixels /
+        active_pixels / stopped_nan / stopped_converged_or_masked / stopped_now."""
+        rule = _adapt_rule(abs_tol, rel_tol, min_chunks, nan, converged)
+        s = _rt.rt_adapt_stats()
+        _rt._check(_rt.lib().rt_frame_adapt(self._handle(), C.byref(rule), C.byref(s)), "rt_frame_adapt")
+        self.active_pixels = s.active_pixels
+        return _adapt_dict(s)
+
+    def stop(self, mask) -> dict:
+        """rt_frame_stop: stops the pixels where mask[H,W] is nonzero (the caller's own rule). Stats as `adapt`."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != (self.height, self.width):
+            raise ValueError(f"expected a mask of shape {(self.height, self.width)}, got {m.shape}")
+        s = _rt.rt_adapt_stats()
+        _rt._check(_rt.lib().rt_frame_stop(self._handle(), m.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(s)),
+                   "rt_frame_stop")
+        self.active_pixels = s.active_pixels
+        return _adapt_dict(s)
+
+    def chunk_counts(self) -> np.ndarray:
+        """rt_frame_chunk_counts: K_p[H,W] (int32), the chunks each pixel's sums hold: where it was stopped,
+        else chunks_done."""
+        k = np.zeros((self.height, self.width), dtype=np.int32)
+        _rt._check(_rt.lib().rt_frame_chunk_counts(self._handle(), k.ctypes.data_as(C.POINTER(C.c_int32))),
+                   "rt_frame_chunk_counts")
+        return k
+
     def close(self):
         # (rt_destroy closes the ctx's open frames itself: after Context.close the handle is dead)
         if self._h is not None and self._ctx._h is not None:
@@ -182,6 +228,29 @@ def error_estimate(sums, moments, chunks_done: int, samples_done: int, abs_tol: 
     return se, _error_dict(st)
 
 
+def adapt_decide(sums, moments, chunks_in, chunks_done: int, chunk: int, spp: int, abs_tol: float = 0.0,
+                 rel_tol: float = 0.0, min_chunks: int = 2, nan: bool = True, converged: bool = True):
+    """rt_adapt_decide (host only): (chunks_out, stats dict) by the rule `ProgressiveFrame.adapt` runs on the
+    device, from image-order sums [..., 3] at `chunks_done` chunks. `moments` may be None without
+    `converged`; `chunks_in` (the K_p map so far, 0 = active) may be None."""
+    s = _doubles(sums)
+    if s.ndim < 1 or s.shape[-1] != 3:
+        raise ValueError("sums must have 3 channels in their last axis")
+    q = None if moments is None else _doubles(moments, s.shape)
+    kin = None if chunks_in is None else np.ascontiguousarray(chunks_in, dtype=np.int32)
+    if kin is not None and kin.shape != s.shape[:-1]:
+        raise ValueError(f"expected chunks_in of shape {s.shape[:-1]}, got {kin.shape}")
+    out = np.zeros(s.shape[:-1], dtype=np.int32)
+    rule = _adapt_rule(abs_tol, rel_tol, min_chunks, nan, converged)
+    st = _rt.rt_adapt_stats()
+    PD, PI = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _rt._check(_rt.lib().rt_adapt_decide(s.ctypes.data_as(PD), None if q is None else q.ctypes.data_as(PD),
+                                         None if kin is None else kin.ctypes.data_as(PI), s.size // 3,
+                                         int(chunks_done), int(chunk), int(spp), C.byref(rule), out.ctypes.data_as(PI),
+                                         C.byref(st)), "rt_adapt_decide")
+    return out, _adapt_dict(st)
+
+
 def blob_info(blob: bytes) -> dict:
     """rt_frame_blob_info: a saved frame's header, validated on the host (no device). Raises RTError
     (RT_E_INVALID) for a malformed blob."""
@@ -201,7 +270,8 @@ def blob_info(blob: bytes) -> dict:
 def render_progressive(ctx, cam, params, step_chunks: int,
                        stop_changed_fraction: Optional[float] = None, *,
                        stop_unconverged_fraction: Optional[float] = None, abs_tol: float = 0.0,
-                       rel_tol: float = 0.0) -> Iterator[Tuple[np.ndarray, dict]]:
+                       rel_tol: float = 0.0, adaptive: bool = False,
+                       min_chunks: int = 2) -> Iterator[Tuple[np.ndarray, dict]]:
     """Yields (rgb, stats) after each step of `step_chunks` chunks. Stops at completion, or once
     bytes_changed / (3*W*H) of a step is at most `stop_changed_fraction` (the 8-bit stopping rule: the
     bytes stopped moving). `ctx` needs `open_frame(cam, params)` returning a frame with `advance`,
@@ -211,12 +281,18 @@ def render_progressive(ctx, cam, params, step_chunks: int,
     chunks_done >= 2 merges `frame.error(abs_tol, rel_tol, want_map=False)`'s stats into the yielded
     dict, and the loop also stops once unconverged_pixels <= fraction * (pixels - nonfinite_pixels): the
     standard error of all but that share of the finite pixels is within abs_tol + rel_tol * |mean|.
-    Either rule stops the loop."""
+    Either rule stops the loop.
+
+    With `adaptive` the frame is opened with `moments=True` and after each step's resolve
+    `frame.adapt(abs_tol, rel_tol, min_chunks)` stops the NaN pixels and the pixels converged under the
+    tolerances (its stats are merged into the yielded dict; the yielded image is the one before that call,
+    which a stop does not change); the loop also ends once no pixel is active."""
     if step_chunks < 1:
         raise ValueError("step_chunks must be at least 1")
     channels = 3 * params.width * params.height
     by_error = stop_unconverged_fraction is not None
-    frame = ctx.open_frame(cam, params, moments=True) if by_error else ctx.open_frame(cam, params)
+    tracked = by_error or adaptive
+    frame = ctx.open_frame(cam, params, moments=True) if tracked else ctx.open_frame(cam, params)
     try:
         while not frame.complete:
             frame.advance(step_chunks)
@@ -226,6 +302,10 @@ def render_progressive(ctx, cam, params, step_chunks: int,
                 err = frame.error(abs_tol, rel_tol, want_map=False)[1]
                 stats.update(err)
                 met = err["unconverged_pixels"] <= stop_unconverged_fraction * (err["pixels"] - err["nonfinite_pixels"])
+            if adaptive:
+                ad = frame.adapt(abs_tol, rel_tol, min_chunks)
+                stats.update(ad)
+                met = met or ad["active_pixels"] == 0
             yield rgb, stats
             if met or (stop_changed_fraction is not None and stats["bytes_changed"] <= stop_changed_fraction * channels):
                 break
