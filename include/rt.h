@@ -656,9 +656,61 @@ int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
  *             RT_E_INVALID: a null sums or rule, a bad rule, pixels < 1, chunks_done outside
  *             [1, ceil(spp / chunk)], a chunks_in value outside [0, chunks_done].
  *
- * Not covered: sharded or multi-device frames, reactivating a stopped pixel, adaptive one-shot rt_render,
- * saving an adapted frame, error estimates and adaptive sampling for tier A, and extending a frame past its
- * spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its per-chunk meaning.
+ * Shard frames: a progressive frame over the slab of (tile, shard_rank, shard_count), the tile shard of
+ * rt_render_shard_async. Its sums, moments, K_p, previews and error map are per slab pixel, and its outputs
+ * are slabs left in device memory, so the gather of the caller's choice and rt_assemble[_linear]_async merge
+ * N shard frames into exactly what an unsharded frame of the same (scene, camera, params, stop calls) gives,
+ * bit for bit (tier B is shard-invariant). The frames of one image may live on different ctxs, devices or
+ * processes; each is advanced, adapted and stopped on its own, and they agree as long as the callers make the
+ * same stop calls at the same chunks_done. Slots of a slab outside the image (tile padding, and the tiles past
+ * the last one when shard_count does not divide the tile count) are never read by assemble: their content
+ * in every output below is unspecified.
+ * open_shard     rt_frame_open_ex that honours p->tile, p->shard_rank and p->shard_count (checked as
+ *                rt_shard_geometry checks them; RT_E_INVALID). CH and chunks_total are the whole image's
+ *                (rt_sample_chunk(width*height, spp)). The frame owns slab_pixels of sums, and of Q with
+ *                RT_FRAME_MOMENTS. Tier A: RT_E_UNSUPPORTED. A frame opened this way is a shard frame even at
+ *                shard_count 1. On a multi-device ctx it acts on the first device.
+ * advance        As above, over the shard's tiles. A shard that owns no image pixel (more shards than tiles)
+ *                launches nothing and still counts the chunks.
+ * resolve_shard  The preview over the samples so far into caller device buffers: d_slab_rgb8 slab_pixels*3
+ *                bytes, d_slab_linear slab_pixels*3 doubles; either may be NULL, both NULL is a stats poll.
+ *                Blocking. nan_pixels and bytes_changed count the shard's own image pixels (the frame keeps its
+ *                previous preview in slab order); summed over the shards they are the unsharded frame's counts.
+ * error_shard    rt_frame_error's map (d_slab_se: slab_pixels*3 doubles of device memory, may be NULL) and
+ *                summary over the shard's pixels, per pixel at (K_p, N_p). pixels = the image pixels the shard
+ *                owns. Counts and max_se are exact; mean_se is added in a fixed order with no floating-point
+ *                atomics, so every call returns the same value.
+ * merging stats  rt_error_stats_merge (host only): counts are added, max_se is the maximum, mean_se is the mean
+ *                weighted by finite pixels, sum_r mean_r * (pixels_r - nonfinite_r) / sum_r (pixels_r -
+ *                nonfinite_r), or 0 when there are none; it agrees with rt_error_estimate over the whole image
+ *                to 1e-12 relative. RT_E_INVALID when the parts disagree in chunks_done or samples_done.
+ *                rt_frame_stats and rt_adapt_stats of the shards merge by plain addition of their counts
+ *                (nan_pixels, bytes_changed; pixels, active_pixels, stopped_nan, stopped_converged_or_masked,
+ *                stopped_now); kernel_ms is per shard.
+ * adapt, stop    Work on shard frames as above: stop takes the same image-order H*W mask and reads only the
+ *                shard's own pixels; the stats are over the shard's pixels (pixels = owned image pixels).
+ * shard_state    Device copies of S and Q (3 doubles per slab pixel) and K_p (int32 per slab pixel; an active
+ *                pixel: chunks_done) in slab order; each pointer may be NULL. d_slab_moments on an untracked
+ *                frame: RT_E_STATE. Blocking.
+ * save_header    The 288-byte header of the frame's whole-image version-1 blob (cap >= RT_FRAME_BLOB_HEADER, else
+ *                RT_E_INVALID): the shard fields are written as 0 / 1, every other field as rt_frame_save writes
+ *                it, so the header is the same on every shard. The caller appends the assembled image-order
+ *                sums (shard_state's S through rt_assemble_linear_async): header + sums is the unsharded frame's
+ *                blob byte for byte. RT_E_STATE on a frame with stopped pixels, as save. Works on unsharded
+ *                frames too.
+ * restore_shard  A shard frame (shard_rank of shard_count) from a whole-image version-1 blob, the tile being the
+ *                blob's; `moments` (optional) is image order, H*W*3 doubles, as for restore_ex. Only the owned
+ *                pixels are taken. The payload is tile-independent, so a checkpoint of N shards resumes on M.
+ *                Fingerprint and upload-flag checks as rt_frame_restore.
+ * kinds          rt_frame_resolve, rt_frame_save, rt_frame_moments, rt_frame_chunk_counts and rt_frame_error
+ *                return RT_E_STATE on a shard frame (the message names the call to use); resolve_shard,
+ *                error_shard and shard_state return RT_E_STATE on an unsharded frame.
+ *
+ * Not covered: frames spanning the devices of an rt_create_multi ctx (a shard frame acts on one device; the
+ * caller gathers), reactivating a stopped pixel, adaptive one-shot rt_render, saving an adapted frame (no blob
+ * version carries K_p or Q), compacting a mostly stopped frame's work-items, error estimates and adaptive
+ * sampling for tier A, and extending a frame past its spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its
+ * per-chunk meaning.
  */
 #define RT_FRAME_BLOB_VERSION 1u
 #define RT_FRAME_BLOB_HEADER 288
@@ -736,6 +788,16 @@ int rt_frame_chunk_counts(rt_frame* f, int32_t* out_chunks);
 int rt_adapt_decide(const double* sums, const double* moments, const int32_t* chunks_in, int64_t pixels,
                     int chunks_done, int chunk, int spp, const rt_adapt_rule* rule, int32_t* chunks_out,
                     rt_adapt_stats* out);
+/* Shard frames (above). The d_* pointers are device memory on the frame's device. */
+int rt_frame_open_shard(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, uint32_t frame_flags,
+                        rt_frame** out);
+int rt_frame_resolve_shard(rt_frame* f, uint8_t* d_slab_rgb8, double* d_slab_linear, rt_frame_stats* out);
+int rt_frame_error_shard(rt_frame* f, const rt_error_tol* tol, double* d_slab_se, rt_error_stats* out);
+int rt_error_stats_merge(const rt_error_stats* parts, int n, rt_error_stats* out);
+int rt_frame_shard_state(rt_frame* f, double* d_slab_sums, double* d_slab_moments, int32_t* d_slab_chunks);
+int rt_frame_save_header(rt_frame* f, void* buf, size_t cap);
+int rt_frame_restore_shard(rt_ctx* ctx, const void* buf, size_t len, const double* moments, int shard_rank,
+                           int shard_count, rt_frame** out);
 /* The fingerprint rt_upload_scene records for a descriptor (host only; the blob's field at 272). */
 int rt_scene_fingerprint(const rt_scene_desc* desc, uint64_t* out);
 /* The chunking of a tier-B frame of `pixels` pixels at `spp` samples (host only): *out_chunk =

@@ -91,4 +91,37 @@ int rt_adapt_decide(const double* sums, const double* moments, const int32_t* ch
   return RT_OK;
 }
 
+int rt_error_stats_merge(const rt_error_stats* parts, int n, rt_error_stats* out) {
+  if (!parts || !out || n < 1) {
+    rt::set_error("rt_error_stats_merge: needs parts, n >= 1 and an output");
+    return RT_E_INVALID;
+  }
+  rt_error_stats st{};
+  st.chunks_done = parts[0].chunks_done;
+  st.samples_done = parts[0].samples_done;
+  double total = 0.0;  // (the parts' mean * finite pixels, in part order)
+  int64_t finite = 0;
+  for (int r = 0; r < n; ++r) {
+    const rt_error_stats& p = parts[r];
+    if (p.chunks_done != st.chunks_done || p.samples_done != st.samples_done) {
+      rt::set_error("rt_error_stats_merge: the parts disagree in chunks_done or samples_done");
+      return RT_E_INVALID;
+    }
+    if (p.pixels < 0 || p.nonfinite_pixels < 0 || p.nonfinite_pixels > p.pixels) {
+      rt::set_error("rt_error_stats_merge: a part's pixel counts are out of range");
+      return RT_E_INVALID;
+    }
+    st.pixels += p.pixels;
+    st.nonfinite_pixels += p.nonfinite_pixels;
+    st.unconverged_pixels += p.unconverged_pixels;
+    if (p.max_se > st.max_se) st.max_se = p.max_se;
+    const int64_t fin = p.pixels - p.nonfinite_pixels;
+    if (fin) total += p.mean_se * (double)fin;
+    finite += fin;
+  }
+  st.mean_se = finite ? total / (double)finite : 0.0;
+  *out = st;
+  return RT_OK;
+}
+
 }  // extern "C"

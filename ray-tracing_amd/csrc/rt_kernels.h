@@ -1155,6 +1155,162 @@ __global__ void __launch_bounds__(256) frame_error_sum(const double* block_sums,
   if (threadIdx.x == 0) *out = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
 }
 
+// ---------------------------------------------------------------- shard frames (rt_frame_*_shard)
+// A shard frame (rt.h) is a progressive frame over the slab of (tile, shard_rank, shard_count): its sums,
+// moments, K_p, previews and error map all stay in slab order, and these kernels run one thread per slab
+// pixel through work_pixel, as adapt_body does (A's frame geometry: fill_frame_geometry with the shard).
+// A slab pixel outside the image, or of a tile past the image's last (more shards than tiles), is padding:
+// never read, never written, never counted. Reads and writes are contiguous in the slab.
+
+// Two per-wave counts (a wave's ballots, already popcounted) summed over the block's 4 waves through LDS;
+// they leave the block as at most one atomic per counter (frame_resolve's reduction).
+__device__ __forceinline__ void block_add2(unsigned a, unsigned b, unsigned long long* counts) {
+  __shared__ unsigned wave_a[4], wave_b[4];
+  if ((threadIdx.x & 63) == 0) {
+    wave_a[threadIdx.x >> 6] = a;
+    wave_b[threadIdx.x >> 6] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned ba = wave_a[0] + wave_a[1] + wave_a[2] + wave_a[3];
+    const unsigned bb = wave_b[0] + wave_b[1] + wave_b[2] + wave_b[3];
+    if (ba) atomicAdd(&counts[0], (unsigned long long)ba);
+    if (bb) atomicAdd(&counts[1], (unsigned long long)bb);
+  }
+}
+
+// frame_resolve in slab order: A.out_rgb / A.out_lin are the shard frame's own slab*3 preview buffers
+// (A.out_rgb holds the previous preview), the per-pixel arithmetic is resolve_body's, so the assembled
+// slabs of all shards are the unsharded preview bit for bit and the counts add up to its counts.
+template <bool ADAPT>
+__device__ __forceinline__ void resolve_slab_body(const LaunchConst& A, int samples, unsigned long long* counts,
+                                                  const int* kp) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool nan = false, c0 = false, c1 = false, c2 = false;
+  int px, row;
+  if (idx < A.slab && work_pixel(A, (uint32_t)idx, px, row)) {
+    const V3 sum = vload(A.acc + idx * 3);
+    nan = sum.x != sum.x || sum.y != sum.y || sum.z != sum.z;
+    if constexpr (ADAPT) {
+      const long long n = (long long)kp[idx] * A.chunk;
+      if (n) samples = n < A.spp ? (int)n : A.spp;
+    }
+    const V3 avg = divide(sum, (double)samples);
+    const uint8_t p0 = A.out_rgb[idx * 3 + 0], p1 = A.out_rgb[idx * 3 + 1], p2 = A.out_rgb[idx * 3 + 2];
+    store_pixel(A, idx, avg);
+    c0 = scale_color(avg.x) != p0;
+    c1 = scale_color(avg.y) != p1;
+    c2 = scale_color(avg.z) != p2;
+  }
+  const unsigned n_nan = (unsigned)__popcll(__ballot(nan));
+  const unsigned n_chg = (unsigned)(__popcll(__ballot(c0)) + __popcll(__ballot(c1)) + __popcll(__ballot(c2)));
+  block_add2(n_nan, n_chg, counts);
+}
+__global__ void __launch_bounds__(256) frame_resolve_slab(LaunchConst A, int samples, unsigned long long* counts) {
+  resolve_slab_body<false>(A, samples, counts, nullptr);
+}
+__global__ void __launch_bounds__(256) frame_resolve_slab_adapt(LaunchConst A, int samples,
+                                                                unsigned long long* counts, const int* kp) {
+  resolve_slab_body<true>(A, samples, counts, kp);
+}
+
+// frame_error in slab order: sums A.acc and `moments` by slab pixel, se stored by slab pixel in `out_se`
+// (the caller's device buffer, may be null; padding slots are left alone). acc[0..2] and block_sums as
+// error_body fills them: exact counts and maximum, and one partial sum per block in a fixed order (a
+// pixel's channels, a wave's lanes by halving shuffles, the waves in wave order) for frame_error_sum, so
+// the shard's mean has no floating-point atomic in it and repeats.
+template <bool ADAPT>
+__device__ __forceinline__ void error_slab_body(const LaunchConst& A, const double* moments, double* out_se,
+                                                int chunks, int samples, double abs_tol, double rel_tol,
+                                                unsigned long long* acc, double* block_sums, const int* kp) {
+  __shared__ unsigned long long wave_max[4];
+  __shared__ double wave_sum[4];
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool bad = false, open = false;
+  double sum = 0.0;
+  unsigned long long top = 0ull;
+  int px, row;
+  if (idx < A.slab && work_pixel(A, (uint32_t)idx, px, row)) {
+    const double s[3] = {A.acc[idx * 3], A.acc[idx * 3 + 1], A.acc[idx * 3 + 2]};
+    const double q[3] = {moments[idx * 3], moments[idx * 3 + 1], moments[idx * 3 + 2]};
+    double se[3];
+    if constexpr (ADAPT) {
+      const int k = kp[idx];
+      if (k) {
+        const long long n = (long long)k * A.chunk;
+        chunks = k;
+        samples = n < A.spp ? (int)n : A.spp;
+      }
+    }
+    int cls = rt::kPixelNonFinite;
+    if (!ADAPT || chunks >= 2) {
+      cls = rt::pixel_error(s, q, chunks, samples, abs_tol, rel_tol, se);
+    } else {
+      se[0] = se[1] = se[2] = __longlong_as_double(0x7ff8000000000000ll);
+    }
+    if (out_se) {
+      out_se[idx * 3 + 0] = se[0];
+      out_se[idx * 3 + 1] = se[1];
+      out_se[idx * 3 + 2] = se[2];
+    }
+    bad = cls == rt::kPixelNonFinite;
+    open = cls == rt::kPixelUnconverged;
+    if (!bad) {
+      sum = (se[0] + se[1]) + se[2];
+      const double m = fmax(fmax(se[0], se[1]), se[2]);
+      top = (unsigned long long)__double_as_longlong(m);
+    }
+  }
+  const unsigned n_bad = (unsigned)__popcll(__ballot(bad)), n_open = (unsigned)__popcll(__ballot(open));
+  for (int off = 32; off > 0; off >>= 1) {
+    sum = sum + __shfl_down(sum, off, 64);
+    const unsigned long long other = __shfl_down(top, off, 64);
+    top = other > top ? other : top;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    wave_max[threadIdx.x >> 6] = top;
+    wave_sum[threadIdx.x >> 6] = sum;
+  }
+  block_add2(n_bad, n_open, acc);  // (its barrier publishes wave_max and wave_sum too)
+  if (threadIdx.x == 0) {
+    unsigned long long m = wave_max[0];
+    for (int w = 1; w < 4; ++w) m = wave_max[w] > m ? wave_max[w] : m;
+    if (m) atomicMax(&acc[2], m);
+    block_sums[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+  }
+}
+__global__ void __launch_bounds__(256) frame_error_slab(LaunchConst A, const double* moments, double* out_se,
+                                                        int chunks, int samples, double abs_tol, double rel_tol,
+                                                        unsigned long long* acc, double* block_sums) {
+  error_slab_body<false>(A, moments, out_se, chunks, samples, abs_tol, rel_tol, acc, block_sums, nullptr);
+}
+__global__ void __launch_bounds__(256) frame_error_slab_adapt(LaunchConst A, const double* moments, double* out_se,
+                                                              int chunks, int samples, double abs_tol,
+                                                              double rel_tol, unsigned long long* acc,
+                                                              double* block_sums, const int* kp) {
+  error_slab_body<true>(A, moments, out_se, chunks, samples, abs_tol, rel_tol, acc, block_sums, kp);
+}
+
+// Saved sums or moments (image order, the whole image) into a shard frame's slab: each slab pixel the shard
+// owns fetches its image pixel (rt_frame_restore_shard); the other shards' pixels are not touched.
+__global__ void __launch_bounds__(256) frame_scatter_slab(LaunchConst A, const double* image, double* sums) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  int px, row;
+  if (idx >= A.slab || !work_pixel(A, (uint32_t)idx, px, row)) return;
+  const long long i = (long long)row * A.W + px;
+  sums[idx * 3 + 0] = image[i * 3 + 0];
+  sums[idx * 3 + 1] = image[i * 3 + 1];
+  sums[idx * 3 + 2] = image[i * 3 + 2];
+}
+
+// K_p in slab order (rt_frame_shard_state): a stopped pixel's kp, else the frame's K; kp null: no stop call yet.
+__global__ void __launch_bounds__(256) frame_chunk_counts_slab(const int* kp, int* out, long long slab, int K) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= slab) return;
+  const int k = kp ? kp[idx] : 0;
+  out[idx] = k ? k : K;
+}
+
 // ---------------------------------------------------------------- debug: closest hits
 template <unsigned F>
 __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* rays, int n, double tmin,

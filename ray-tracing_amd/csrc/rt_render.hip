@@ -111,6 +111,11 @@ struct rt_frame {
   rt_render_params p{};
   int chunk = 0, chunks_total = 0, chunks_done = 0;
   long long slab = 0, npx = 0;
+  // A shard frame (rt_frame_open_shard, rt_frame_restore_shard): `p` keeps its shard fields, the slab is
+  // that shard's, and the previews and the error map stay in slab order (d_rgb, d_lin: slab*3). `owned` =
+  // the image pixels in the frame's slab (an unsharded frame: npx).
+  bool shard = false;
+  long long owned = 0;
   double* d_sum = nullptr;   // [slab pixel][3]
   uint8_t* d_rgb = nullptr;  // the last preview's bytes (zero before the first), H*W*3
   double* d_lin = nullptr;   // the last linear preview, H*W*3
@@ -1274,15 +1279,65 @@ void frame_free(rt_frame* f) {
   delete f;
 }
 
+// Image pixels in the slab of shard (p.shard_rank, p.shard_count): its tiles, clipped to the image.
+long long owned_pixels(const rt_render_params& p) {
+  int tile, tiles_x;
+  long long tt, ps, slab, n = 0;
+  geometry(&p, tile, tiles_x, tt, ps, slab);
+  const int shards = p.shard_count > 0 ? p.shard_count : 1;
+  for (long long gt = p.shard_rank; gt < tt; gt += shards) {
+    const long long ty = gt / tiles_x, tx = gt % tiles_x;
+    n += std::min<long long>(tile, p.width - tx * tile) * std::min<long long>(tile, p.height - ty * tile);
+  }
+  return n;
+}
+
+// Image-order calls take unsharded frames, the _shard calls shard frames (rt.h): RT_E_STATE otherwise,
+// naming the call to use instead.
+int frame_kind(const rt_frame* f, bool shard, const char* what, const char* instead) {
+  if (f->shard == shard) return RT_OK;
+  return state_error(std::string(what) + (shard ? ": not a shard frame (rt_frame_open_shard); use "
+                                                : ": a shard frame keeps slab order; use ") + instead);
+}
+
+// The header of the frame's whole-image version-1 blob (rt.h): a shard frame's is the unsharded frame's,
+// its shard fields written as 0 / 1.
+void frame_write_header(const rt_frame* f, uint8_t* buf) {
+  rt_frame_blob_desc b{};
+  b.version = RT_FRAME_BLOB_VERSION;
+  b.upload_flags = f->ctx->upload_flags;
+  b.params = f->p;
+  b.params.shard_rank = 0;
+  b.params.shard_count = 1;
+  b.camera = f->cam;
+  b.chunk = f->chunk;
+  b.chunks_done = f->chunks_done;
+  b.pixels = f->npx;
+  b.scene_fingerprint = f->ctx->fingerprint;
+  b.payload_bytes = sizeof(double) * 3 * (size_t)f->npx;
+  rt::blob_write_header(b, buf);
+}
+
+// The frame's geometry and sums in launch constants, for the slab-order kernels of a shard frame.
+void shard_const(const rt_frame* f, LaunchConst& A) {
+  long long per_shard;
+  fill_frame_geometry(A, &f->p, f->p.shard_rank, f->p.shard_count, per_shard);
+  A.chunk = f->chunk;  // (rt.h's, whatever RTAMD_CHUNK says: frame_new refuses the override)
+  A.acc = f->d_sum;
+}
+
 // A frame of `p` on c with zero sums and a zero previous preview, registered on the ctx; with
 // RT_FRAME_MOMENTS in `frame_flags`, zero second moments too.
 int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, uint32_t frame_flags, const char* what,
-              rt_frame** out) {
+              rt_frame** out, bool shard = false) {
   if (frame_flags & ~RT_FRAME_MOMENTS) return invalid(std::string(what) + ": unknown frame flag");
   rt_render_params p = *pin;  // whole image: the shard fields are ignored
-  p.shard_rank = 0;
-  p.shard_count = 1;
+  if (!shard) {
+    p.shard_rank = 0;
+    p.shard_count = 1;
+  }
   int rc = check_params(&p);
+  if (!rc && shard && p.shard_count == 0) p.shard_count = 1;  // (0 means unsharded, as in rt_shard_geometry)
   if (rc) return rc;
   if (p.rng_mode != RT_RNG_PHILOX)
     return unsupported(std::string(what) + ": progressive frames are tier B (RT_RNG_PHILOX) only");
@@ -1297,19 +1352,23 @@ int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, uint
   long long tt, ps;
   geometry(&p, tile, tiles_x, tt, ps, f->slab);
   f->npx = (long long)p.width * p.height;
+  f->shard = shard;
+  f->owned = shard ? owned_pixels(p) : f->npx;
   f->chunk = rt_sample_chunk((int64_t)f->npx, p.spp);
   f->chunks_total = (p.spp + f->chunk - 1) / f->chunk;
   f->last.chunk = f->chunk;
   f->last.chunks_total = f->chunks_total;
   f->last.chunks_done = -1;  // (no resolve yet)
   auto init = [&]() -> int {
-    const size_t sums = sizeof(double) * 3 * (size_t)f->slab, img = (size_t)f->npx * 3;
+    // (a shard frame's previews are slab order; their padding slots are zeroed once and never written)
+    const size_t sums = sizeof(double) * 3 * (size_t)f->slab, img = (size_t)(shard ? f->slab : f->npx) * 3;
     HIPCHK(hipMalloc((void**)&f->d_sum, sums));
     HIPCHK(hipMalloc((void**)&f->d_rgb, img));
     HIPCHK(hipMalloc((void**)&f->d_lin, sizeof(double) * img));
     HIPCHK(hipMalloc((void**)&f->d_counts, 2 * sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(f->d_sum, 0, sums, c->stream));
     HIPCHK(hipMemsetAsync(f->d_rgb, 0, img, c->stream));
+    if (shard) HIPCHK(hipMemsetAsync(f->d_lin, 0, sizeof(double) * img, c->stream));
     if (frame_flags & RT_FRAME_MOMENTS) {
       HIPCHK(hipMalloc((void**)&f->d_q, sums));
       HIPCHK(hipMemsetAsync(f->d_q, 0, sums, c->stream));
@@ -1347,7 +1406,7 @@ int frame_stop_call(rt_frame* f, const rt_adapt_rule* rule, const uint8_t* mask,
   }
   LaunchConst A{};
   long long per_shard;
-  fill_frame_geometry(A, &f->p, 0, 1, per_shard);
+  fill_frame_geometry(A, &f->p, f->p.shard_rank, f->p.shard_count, per_shard);  // (unsharded: 0 of 1)
   A.acc = f->d_sum;
   int K = f->chunks_done, N = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
   unsigned long long* d_counts = f->d_adapt;
@@ -1371,7 +1430,7 @@ int frame_stop_call(rt_frame* f, const rt_adapt_rule* rule, const uint8_t* mask,
   if (out) {
     rt_adapt_stats st{};
     st.chunks_done = f->chunks_done;
-    st.pixels = (int64_t)f->npx;
+    st.pixels = (int64_t)f->owned;
     st.stopped_nan = f->stopped_nan;
     st.stopped_converged_or_masked = f->stopped_other;
     st.active_pixels = st.pixels - st.stopped_nan - st.stopped_converged_or_masked;
@@ -1404,7 +1463,12 @@ int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
   if (max_chunks < 0) return invalid("rt_frame_advance: max_chunks must not be negative");
   const int n = std::min(max_chunks, f->chunks_total - f->chunks_done);
   if (n == 0) return RT_OK;  // (a complete frame: nothing left to render)
-  if (f->stopped_nan + f->stopped_other == f->npx) return RT_OK;  // (an adaptive frame with no active pixel)
+  if (f->shard && f->owned == 0) {  // (more shards than tiles: nothing to launch, the chunks still count)
+    f->chunks_done += n;
+    if (out_now) *out_now = n;
+    return RT_OK;
+  }
+  if (f->stopped_nan + f->stopped_other == f->owned) return RT_OK;  // (an adaptive frame with no active pixel)
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
   if (f->used == f->events.size()) {
@@ -1425,7 +1489,8 @@ int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
   span.skip = f->d_skip;
   span.ev_begin = f->events[f->used].first;
   span.ev_end = f->events[f->used].second;
-  rc = launch_philox(c, &f->cam, &f->p, 0, 1, nullptr, nullptr, c->stream, nullptr, nullptr, span);
+  rc = launch_philox(c, &f->cam, &f->p, f->p.shard_rank, f->p.shard_count, nullptr, nullptr, c->stream, nullptr,
+                     nullptr, span);  // (unsharded: shard 0 of 1)
   if (rc) {  // (some of the step's launches may have been folded in: the sums are no longer a frame's)
     f->valid = false;
     return rc;
@@ -1439,6 +1504,7 @@ int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
 int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb, double* out_lin, rt_frame_stats* out) {
   int rc = frame_live(f, "rt_frame_resolve");
   if (rc) return rc;
+  if ((rc = frame_kind(f, false, "rt_frame_resolve", "rt_frame_resolve_shard"))) return rc;
   if (f->chunks_done == 0) return state_error("rt_frame_resolve: no chunk rendered yet");
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
@@ -1488,6 +1554,7 @@ int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb, double* out_lin, rt_frame_st
 int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len) {
   int rc = frame_live(f, "rt_frame_save");
   if (rc) return rc;
+  if ((rc = frame_kind(f, false, "rt_frame_save", "rt_frame_save_header and rt_frame_shard_state"))) return rc;
   if (f->stopped_nan + f->stopped_other > 0)
     return state_error("rt_frame_save: the frame has stopped pixels (the version-1 blob has no room for their chunk counts)");
   const size_t payload = sizeof(double) * 3 * (size_t)f->npx;
@@ -1496,17 +1563,7 @@ int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len) {
   if (!buf || cap < need) return RT_OK;  // (size query)
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
-  rt_frame_blob_desc b{};
-  b.version = RT_FRAME_BLOB_VERSION;
-  b.upload_flags = c->upload_flags;
-  b.params = f->p;
-  b.camera = f->cam;
-  b.chunk = f->chunk;
-  b.chunks_done = f->chunks_done;
-  b.pixels = f->npx;
-  b.scene_fingerprint = c->fingerprint;
-  b.payload_bytes = payload;
-  rt::blob_write_header(b, (uint8_t*)buf);
+  frame_write_header(f, (uint8_t*)buf);
   // the sums in image order (assemble's map at one shard), staged on the device, then copied out
   static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the blob's payload is copied as the host's doubles");
   if (!f->d_stage) HIPCHK(hipMalloc((void**)&f->d_stage, payload));  // (kept: a checkpoint per step allocates once)
@@ -1566,6 +1623,7 @@ int rt_frame_restore_ex(rt_ctx* c, const void* buf, size_t len, const double* mo
 int rt_frame_moments(rt_frame* f, double* out_q) {
   int rc = frame_live(f, "rt_frame_moments");
   if (rc) return rc;
+  if ((rc = frame_kind(f, false, "rt_frame_moments", "rt_frame_shard_state"))) return rc;
   if (!out_q) return invalid("rt_frame_moments: null argument");
   if (!f->d_q) return state_error("rt_frame_moments: the frame was opened without RT_FRAME_MOMENTS");
   if (f->chunks_done == 0) return state_error("rt_frame_moments: no chunk rendered yet");
@@ -1587,6 +1645,7 @@ int rt_frame_moments(rt_frame* f, double* out_q) {
 int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_error_stats* out) {
   int rc = frame_live(f, "rt_frame_error");
   if (rc) return rc;
+  if ((rc = frame_kind(f, false, "rt_frame_error", "rt_frame_error_shard"))) return rc;
   double abs_tol, rel_tol;
   if (!rt::error_tol(tol, abs_tol, rel_tol)) return invalid("rt_frame_error: abs_tol and rel_tol must be >= 0 and not NaN");
   if (!f->d_q) return state_error("rt_frame_error: the frame was opened without RT_FRAME_MOMENTS");
@@ -1653,6 +1712,7 @@ int rt_frame_stop(rt_frame* f, const uint8_t* mask, rt_adapt_stats* out) {
 int rt_frame_chunk_counts(rt_frame* f, int32_t* out_chunks) {
   int rc = frame_live(f, "rt_frame_chunk_counts");
   if (rc) return rc;
+  if ((rc = frame_kind(f, false, "rt_frame_chunk_counts", "rt_frame_shard_state"))) return rc;
   if (!out_chunks) return invalid("rt_frame_chunk_counts: null argument");
   if (!f->d_kp) {  // (no stop call yet: every pixel is active)
     std::fill(out_chunks, out_chunks + f->npx, (int32_t)f->chunks_done);
@@ -1669,6 +1729,182 @@ int rt_frame_chunk_counts(rt_frame* f, int32_t* out_chunks) {
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpy(out_chunks, f->d_kimg, sizeof(int) * (size_t)f->npx, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+// ---- shard frames (rt.h): a progressive frame over one shard's slab, its outputs left in device memory
+
+int rt_frame_open_shard(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, uint32_t frame_flags,
+                        rt_frame** out) {
+  if (!c || !cam || !p || !out) return invalid("rt_frame_open_shard: null argument");
+  *out = nullptr;
+  return frame_new(c, cam, p, frame_flags, "rt_frame_open_shard", out, true);
+}
+
+int rt_frame_resolve_shard(rt_frame* f, uint8_t* d_slab_rgb8, double* d_slab_linear, rt_frame_stats* out) {
+  int rc = frame_live(f, "rt_frame_resolve_shard");
+  if (rc) return rc;
+  if ((rc = frame_kind(f, true, "rt_frame_resolve_shard", "rt_frame_resolve"))) return rc;
+  if (f->chunks_done == 0) return state_error("rt_frame_resolve_shard: no chunk rendered yet");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  // (nothing rendered since the last resolve: the frame still holds that preview, and its stats repeat)
+  if (f->last.chunks_done != f->chunks_done) {
+    LaunchConst A{};
+    shard_const(f, A);
+    A.out_rgb = f->d_rgb;
+    A.out_lin = f->d_lin;
+    int samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
+    unsigned long long* d_counts = f->d_counts;
+    HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    const int* d_kp = f->d_kp;
+    void* args[] = {&A, &samples, &d_counts, &d_kp};  // (frame_resolve_slab takes the first three)
+    HIPCHK(hipLaunchKernel(d_kp ? (const void*)frame_resolve_slab_adapt : (const void*)frame_resolve_slab,
+                           dim3((unsigned)((f->slab + 255) / 256)), dim3(256), args, 0, c->stream));
+    HIPCHK(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    double ms = 0.0;
+    for (size_t i = 0; i < f->used; ++i) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, f->events[i].first, f->events[i].second));
+      ms += t;
+    }
+    f->used = 0;
+    f->last.chunks_done = f->chunks_done;
+    f->last.samples_done = samples;
+    f->last.kernel_ms = ms;
+    f->last.nan_pixels = (int64_t)counts[0];
+    f->last.bytes_changed = (int64_t)counts[1];
+  }
+  const size_t n3 = (size_t)f->slab * 3;
+  if (d_slab_rgb8) HIPCHK(hipMemcpyAsync(d_slab_rgb8, f->d_rgb, n3, hipMemcpyDeviceToDevice, c->stream));
+  if (d_slab_linear)
+    HIPCHK(hipMemcpyAsync(d_slab_linear, f->d_lin, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
+  if (d_slab_rgb8 || d_slab_linear) HIPCHK(hipStreamSynchronize(c->stream));
+  if (out) *out = f->last;
+  return RT_OK;
+}
+
+int rt_frame_error_shard(rt_frame* f, const rt_error_tol* tol, double* d_slab_se, rt_error_stats* out) {
+  int rc = frame_live(f, "rt_frame_error_shard");
+  if (rc) return rc;
+  if ((rc = frame_kind(f, true, "rt_frame_error_shard", "rt_frame_error"))) return rc;
+  double abs_tol, rel_tol;
+  if (!rt::error_tol(tol, abs_tol, rel_tol))
+    return invalid("rt_frame_error_shard: abs_tol and rel_tol must be >= 0 and not NaN");
+  if (!f->d_q) return state_error("rt_frame_error_shard: the frame was opened without RT_FRAME_MOMENTS");
+  if (f->chunks_done < 2) return state_error("rt_frame_error_shard: the estimate needs at least 2 chunks");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  const int blocks = (int)((f->slab + 255) / 256);
+  if (!f->d_err) HIPCHK(hipMalloc((void**)&f->d_err, sizeof(unsigned long long) * (4 + (size_t)blocks)));
+  LaunchConst A{};
+  shard_const(f, A);
+  int chunks = f->chunks_done, samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
+  unsigned long long* d_acc = f->d_err;
+  double *d_block = reinterpret_cast<double*>(f->d_err + 4), *d_total = reinterpret_cast<double*>(f->d_err + 3);
+  HIPCHK(hipMemsetAsync(d_acc, 0, 4 * sizeof(unsigned long long), c->stream));
+  if (f->d_kp)  // (an adapted frame: each stopped pixel at its own (K_p, N_p))
+    hipLaunchKernelGGL(frame_error_slab_adapt, dim3((unsigned)blocks), dim3(256), 0, c->stream, A,
+                       (const double*)f->d_q, d_slab_se, chunks, samples, abs_tol, rel_tol, d_acc, d_block,
+                       (const int*)f->d_kp);
+  else
+    hipLaunchKernelGGL(frame_error_slab, dim3((unsigned)blocks), dim3(256), 0, c->stream, A, (const double*)f->d_q,
+                       d_slab_se, chunks, samples, abs_tol, rel_tol, d_acc, d_block);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(frame_error_sum, dim3(1), dim3(256), 0, c->stream, (const double*)d_block, blocks, d_total);
+  HIPCHK(hipGetLastError());
+  unsigned long long acc[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (out) {
+    rt_error_stats st{};
+    st.chunks_done = chunks;
+    st.samples_done = samples;
+    st.pixels = (int64_t)f->owned;
+    st.nonfinite_pixels = (int64_t)acc[0];
+    st.unconverged_pixels = (int64_t)acc[1];
+    double total;
+    std::memcpy(&st.max_se, &acc[2], sizeof(double));
+    std::memcpy(&total, &acc[3], sizeof(double));
+    const int64_t finite = st.pixels - st.nonfinite_pixels;
+    st.mean_se = finite ? total / (double)(3 * finite) : 0.0;
+    *out = st;
+  }
+  return RT_OK;
+}
+
+int rt_frame_shard_state(rt_frame* f, double* d_slab_sums, double* d_slab_moments, int32_t* d_slab_chunks) {
+  int rc = frame_live(f, "rt_frame_shard_state");
+  if (rc) return rc;
+  if ((rc = frame_kind(f, true, "rt_frame_shard_state", "rt_frame_save, rt_frame_moments and rt_frame_chunk_counts")))
+    return rc;
+  if (d_slab_moments && !f->d_q)
+    return state_error("rt_frame_shard_state: the frame was opened without RT_FRAME_MOMENTS");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  const size_t bytes = sizeof(double) * 3 * (size_t)f->slab;
+  if (d_slab_sums) HIPCHK(hipMemcpyAsync(d_slab_sums, f->d_sum, bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (d_slab_moments) HIPCHK(hipMemcpyAsync(d_slab_moments, f->d_q, bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (d_slab_chunks) {
+    hipLaunchKernelGGL(frame_chunk_counts_slab, dim3((unsigned)((f->slab + 255) / 256)), dim3(256), 0, c->stream,
+                       (const int*)f->d_kp, (int*)d_slab_chunks, f->slab, f->chunks_done);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_frame_save_header(rt_frame* f, void* buf, size_t cap) {
+  int rc = frame_live(f, "rt_frame_save_header");
+  if (rc) return rc;
+  if (!buf || cap < RT_FRAME_BLOB_HEADER) return invalid("rt_frame_save_header: needs a buffer of RT_FRAME_BLOB_HEADER bytes");
+  if (f->stopped_nan + f->stopped_other > 0)
+    return state_error("rt_frame_save_header: the frame has stopped pixels (the version-1 blob has no room for their chunk counts)");
+  frame_write_header(f, (uint8_t*)buf);
+  return RT_OK;
+}
+
+int rt_frame_restore_shard(rt_ctx* c, const void* buf, size_t len, const double* moments, int shard_rank,
+                           int shard_count, rt_frame** out) {
+  if (!c || !out) return invalid("rt_frame_restore_shard: null argument");
+  *out = nullptr;
+  rt_frame_blob_desc b;
+  int rc = rt_frame_blob_info(buf, len, &b);
+  if (rc) return rc;
+  if (!c->has_scene) return state_error("rt_frame_restore_shard: no scene uploaded");
+  if (b.scene_fingerprint != c->fingerprint || b.upload_flags != c->upload_flags)
+    return state_error("rt_frame_restore_shard: the blob was saved over another scene (fingerprint or upload flags differ)");
+  rt_render_params p = b.params;  // (the blob's tile; the shard is the caller's)
+  p.shard_rank = shard_rank;
+  p.shard_count = shard_count;
+  rt_frame* f = nullptr;
+  if ((rc = frame_new(c, &b.camera, &p, moments ? RT_FRAME_MOMENTS : 0u, "rt_frame_restore_shard", &f, true))) return rc;
+  auto fill = [&]() -> int {
+    DEVICE_SCOPE(c->device);
+    DevBuf stage;  // (the whole image, once per restore: a shard frame keeps no image-order buffer)
+    HIPCHK(hipMalloc(&stage.p, (size_t)b.payload_bytes));
+    LaunchConst A{};
+    shard_const(f, A);
+    const void* src[2] = {(const uint8_t*)buf + RT_FRAME_BLOB_HEADER, moments};
+    double* dst[2] = {f->d_sum, f->d_q};
+    for (int i = 0; i < (moments ? 2 : 1); ++i) {
+      HIPCHK(hipMemcpy(stage.p, src[i], (size_t)b.payload_bytes, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(frame_scatter_slab, dim3((unsigned)((f->slab + 255) / 256)), dim3(256), 0, c->stream, A,
+                         (const double*)stage.p, dst[i]);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return RT_OK;
+  };
+  if ((rc = fill())) {
+    rt_frame_close(f);
+    return rc;
+  }
+  f->chunks_done = b.chunks_done;
+  *out = f;
   return RT_OK;
 }
 

@@ -184,6 +184,8 @@ EXPORTED = [
     "rt_frame_blob_info", "rt_frame_close", "rt_scene_fingerprint", "rt_frame_chunking",
     "rt_frame_open_ex", "rt_frame_moments", "rt_frame_restore_ex", "rt_frame_error", "rt_error_estimate",
     "rt_frame_adapt", "rt_frame_stop", "rt_frame_chunk_counts", "rt_adapt_decide",
+    "rt_frame_open_shard", "rt_frame_resolve_shard", "rt_frame_error_shard", "rt_error_stats_merge",
+    "rt_frame_shard_state", "rt_frame_save_header", "rt_frame_restore_shard",
 ]
 
 # include/rt_wide.h: one 4-wide node (128 B)
@@ -291,6 +293,13 @@ def lib() -> C.CDLL:
             "rt_frame_chunk_counts": (I, [C.c_void_p, P(C.c_int32)]),
             "rt_adapt_decide": (I, [P(D), P(D), P(C.c_int32), C.c_int64, I, I, I, P(rt_adapt_rule), P(C.c_int32),
                                     P(rt_adapt_stats)]),
+            "rt_frame_open_shard": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), C.c_uint32, P(C.c_void_p)]),
+            "rt_frame_resolve_shard": (I, [C.c_void_p, C.c_void_p, C.c_void_p, P(rt_frame_stats)]),
+            "rt_frame_error_shard": (I, [C.c_void_p, P(rt_error_tol), C.c_void_p, P(rt_error_stats)]),
+            "rt_error_stats_merge": (I, [P(rt_error_stats), I, P(rt_error_stats)]),
+            "rt_frame_shard_state": (I, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "rt_frame_save_header": (I, [C.c_void_p, C.c_char_p, C.c_size_t]),
+            "rt_frame_restore_shard": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(D), I, I, P(C.c_void_p)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -652,6 +661,17 @@ class Context:
         taken at that save, the restored frame tracks moments too (rt_frame_restore_ex)."""
         return restore_frame(self, blob, moments)
 
+    def open_shard_frame(self, cam: rt_camera, params: rt_render_params, moments: bool = False) -> "ShardFrame":
+        """rt_frame_open_shard: a progressive frame over the slab of (params.tile, shard_rank, shard_count),
+        whose previews, error map and state stay in slab order in device memory (rtamd.progressive.ShardFrame)."""
+        return ShardFrame.open(self, cam, params, moments=moments)
+
+    def restore_shard_frame(self, blob: bytes, rank: int, count: int,
+                            moments: Optional[np.ndarray] = None) -> "ShardFrame":
+        """rt_frame_restore_shard: shard `rank` of `count` of the frame a whole-image version-1 blob holds (the
+        tile is the blob's; `moments` is image order, as for `restore_frame`)."""
+        return restore_shard_frame(self, blob, rank, count, moments)
+
     def render(self, cam: rt_camera, params: rt_render_params, col_gens: Optional[np.ndarray] = None,
                linear: bool = False, want_gens: bool = False):
         """Full image, blocking. Returns (rgb8[H,W,3], linear[H,W,3] | None, gens[W,2] | None)."""
@@ -884,5 +904,6 @@ def assemble_host(slabs: np.ndarray, params: rt_render_params) -> np.ndarray:
     return img.reshape(H, W, 3)
 
 
-from .progressive import (ProgressiveFrame, adapt_decide, blob_info, error_estimate,  # noqa: E402
-                          render_progressive, restore_frame)
+from .progressive import (ProgressiveFrame, ShardFrame, ShardedProgressiveFrame, adapt_decide,  # noqa: E402
+                          blob_info, error_estimate, error_stats_merge, render_progressive, restore_frame,
+                          restore_shard_frame)

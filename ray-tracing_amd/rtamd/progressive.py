@@ -17,6 +17,11 @@ after two chunks, and `render_progressive(..., stop_unconverged_fraction=...)` s
 Adaptive frames (rt.h): `fr.adapt(...)` stops the pixels whose sum is NaN (nothing is lost: their bytes stay 0)
 and those already converged under a tolerance, `fr.stop(mask)` the caller's own choice; later `advance` calls
 render the active pixels only. `render_progressive(..., adaptive=True)` calls `adapt` after every step.
+
+Shard frames (rt.h): `ctx.open_shard_frame(cam, params)` is the same frame over the slab of one tile shard
+(params.tile, shard_rank, shard_count), its previews, error map and state left in slab order in device memory
+(`ShardFrame`); `ShardedProgressiveFrame` drives `world` of them, in one process or as one rank of a
+torch.distributed group, and gives the unsharded frame's results bit for bit.
 """
 from __future__ import annotations
 
@@ -119,6 +124,13 @@ class ProgressiveFrame:
         buf = C.create_string_buffer(n.value)
         _rt._check(_rt.lib().rt_frame_save(self._handle(), buf, n.value, C.byref(n)), "rt_frame_save")
         return buf.raw[:n.value]
+
+    def save_header(self) -> bytes:
+        """rt_frame_save_header: the 288-byte header of the whole image's version-1 blob (`save()`'s first 288 bytes;
+        on a shard frame the whole image's, the same on every shard)."""
+        buf = C.create_string_buffer(BLOB_HEADER)
+        _rt._check(_rt.lib().rt_frame_save_header(self._handle(), buf, BLOB_HEADER), "rt_frame_save_header")
+        return buf.raw
 
     def moments(self) -> np.ndarray:
         """rt_frame_moments: Q[H,W,3], the second moments of the chunk sums (rt.h), for `restore_frame` and
@@ -311,3 +323,383 @@ def render_progressive(ctx, cam, params, step_chunks: int,
                 break
     finally:
         frame.close()
+
+
+# ----------------------------------------------------------------------------- shard frames (rt.h)
+def error_stats_merge(parts) -> dict:
+    """rt_error_stats_merge (host only): the error stats of N shard frames (dicts with ERROR_FIELDS, or
+    rt_error_stats) as one: counts added, max_se the maximum, mean_se weighted by finite pixels."""
+    parts = list(parts)
+    arr = (_rt.rt_error_stats * max(1, len(parts)))()
+    for i, p in enumerate(parts):
+        for k in ERROR_FIELDS:
+            setattr(arr[i], k, p[k] if isinstance(p, dict) else getattr(p, k))
+    out = _rt.rt_error_stats()
+    _rt._check(_rt.lib().rt_error_stats_merge(arr, len(parts), C.byref(out)), "rt_error_stats_merge")
+    return _error_dict(out)
+
+
+def _dev_ptr(x):
+    """A device pointer argument: None, an integer address, or a torch tensor (contiguous, on the frame's device)."""
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):
+        if not x.is_contiguous():
+            raise ValueError("device buffers must be contiguous")
+        return C.c_void_p(x.data_ptr())
+    return C.c_void_p(int(x))
+
+
+def shard_params(params, rank: int, count: int):
+    """A copy of `params` for shard `rank` of `count`."""
+    p = _rt.rt_render_params()
+    C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+    p.shard_rank, p.shard_count = int(rank), int(count)
+    return p
+
+
+class ShardFrame(ProgressiveFrame):
+    """One shard frame of a Context (rt_frame_open_shard / rt_frame_restore_shard): `advance`, `adapt`, `stop`
+    and `close` as ProgressiveFrame; previews, error map and state are slabs of `slab_pixels` pixels in the
+    layout of rt_render_shard_async, written into device memory (`*_into`: device pointers or torch tensors
+    on the ctx's device) or, by the host conveniences `resolve`, `error` and `state`, returned as numpy slabs.
+    The image-order calls (`save`, `moments`, `chunk_counts`) raise RTError (RT_E_STATE) on it."""
+
+    def __init__(self, ctx, handle, params, tracks_moments: bool = False):
+        super().__init__(ctx, handle, params, tracks_moments)
+        self.params = shard_params(params, params.shard_rank, max(1, params.shard_count))
+        self.rank, self.count = self.params.shard_rank, self.params.shard_count
+        self.slab_pixels = _rt.shard_geometry(self.params)[2]
+        self.owned_pixels = int((_rt.shard_pixel_map(self.params) >= 0).sum())
+        self.active_pixels = self.owned_pixels
+
+    @classmethod
+    def open(cls, ctx, cam, params, moments: bool = False) -> "ShardFrame":
+        h = C.c_void_p()
+        _rt._check(_rt.lib().rt_frame_open_shard(ctx._h, C.byref(cam), C.byref(params),
+                                                 _rt.RT_FRAME_MOMENTS if moments else 0, C.byref(h)),
+                   "rt_frame_open_shard")
+        return cls(ctx, h, params, moments)
+
+    # ---- device outputs
+    def resolve_into(self, rgb=None, linear=None) -> dict:
+        """rt_frame_resolve_shard: the preview into device slabs (uint8 [slab, 3] / float64 [slab, 3]; None:
+        skipped); returns the stats dict, whose counts are over this shard's pixels."""
+        s = _rt.rt_frame_stats()
+        _rt._check(_rt.lib().rt_frame_resolve_shard(self._handle(), _dev_ptr(rgb), _dev_ptr(linear), C.byref(s)),
+                   "rt_frame_resolve_shard")
+        return _stats_dict(s)
+
+    def error_into(self, se=None, abs_tol: float = 0.0, rel_tol: float = 0.0) -> dict:
+        """rt_frame_error_shard: the error map into a device slab (float64 [slab, 3]; None: skipped); returns
+        the stats dict over this shard's pixels (merge them with `error_stats_merge`)."""
+        tol = _rt.rt_error_tol(abs_tol, rel_tol)
+        s = _rt.rt_error_stats()
+        _rt._check(_rt.lib().rt_frame_error_shard(self._handle(), C.byref(tol), _dev_ptr(se), C.byref(s)),
+                   "rt_frame_error_shard")
+        return _error_dict(s)
+
+    def state_into(self, sums=None, moments=None, chunks=None) -> None:
+        """rt_frame_shard_state: device copies of S, Q (float64 [slab, 3]) and K_p (int32 [slab]), slab order."""
+        _rt._check(_rt.lib().rt_frame_shard_state(self._handle(), _dev_ptr(sums), _dev_ptr(moments), _dev_ptr(chunks)),
+                   "rt_frame_shard_state")
+
+    # ---- host conveniences (numpy slabs, staged through torch tensors on the ctx's device)
+    def slab_tensor(self, dtype, channels: int = 3):
+        """A zeroed torch tensor of one slab on the ctx's device: [slab_pixels, channels] (channels 0: [slab_pixels])."""
+        import torch
+        shape = (self.slab_pixels, channels) if channels else (self.slab_pixels,)
+        t = torch.zeros(shape, dtype=dtype, device=f"cuda:{self._ctx.device}")
+        torch.cuda.current_stream(t.device).synchronize()  # (the ctx writes it on its own, non-blocking stream)
+        return t
+
+    def resolve(self, rgb: bool = True, linear: bool = True):
+        """(rgb8[slab,3] | None, linear[slab,3] | None, stats dict): `ProgressiveFrame.resolve` in slab order."""
+        import torch
+        t_rgb = self.slab_tensor(torch.uint8) if rgb else None
+        t_lin = self.slab_tensor(torch.float64) if linear else None
+        st = self.resolve_into(t_rgb, t_lin)
+        return (t_rgb.cpu().numpy() if rgb else None, t_lin.cpu().numpy() if linear else None, st)
+
+    def error(self, abs_tol: float = 0.0, rel_tol: float = 0.0, want_map: bool = True):
+        """(se[slab,3] | None, stats dict): `ProgressiveFrame.error` in slab order over this shard's pixels."""
+        import torch
+        t = self.slab_tensor(torch.float64) if want_map else None
+        st = self.error_into(t, abs_tol, rel_tol)
+        return (t.cpu().numpy() if want_map else None), st
+
+    def state(self, moments: Optional[bool] = None):
+        """(S[slab,3], Q[slab,3] | None, K_p[slab]) as numpy slabs; `moments` defaults to whether the frame tracks them."""
+        import torch
+        want_q = self.tracks_moments if moments is None else moments
+        s, k = self.slab_tensor(torch.float64), self.slab_tensor(torch.int32, 0)
+        q = self.slab_tensor(torch.float64) if want_q else None
+        self.state_into(s, q, k)
+        return s.cpu().numpy(), (q.cpu().numpy() if want_q else None), k.cpu().numpy()
+
+
+def restore_shard_frame(ctx, blob: bytes, rank: int, count: int, moments: Optional[np.ndarray] = None) -> ShardFrame:
+    """rt_frame_restore_shard: shard `rank` of `count` of a whole-image blob's frame (see Context.restore_shard_frame)."""
+    info = blob_info(blob)
+    h = C.c_void_p()
+    q = None if moments is None else _doubles(moments, (info["height"], info["width"], 3))
+    _rt._check(_rt.lib().rt_frame_restore_shard(ctx._h, blob, len(blob),
+                                                None if q is None else q.ctypes.data_as(C.POINTER(C.c_double)),
+                                                int(rank), int(count), C.byref(h)), "rt_frame_restore_shard")
+    fr = ShardFrame(ctx, h, shard_params(info["params"], rank, count), moments is not None)
+    fr.chunks_done = info["chunks_done"]
+    return fr
+
+
+class ShardedProgressiveFrame:
+    """One progressive frame over `world` shard frames, with ProgressiveFrame's surface: `advance`, `resolve`
+    (image, linear, merged stats), `error`, `adapt`, `stop`, `chunk_counts`, `save` (blob, moments), the
+    `restore(..., world=M)` classmethod and `close`. The result is the unsharded frame's, bit for bit.
+
+    Local mode: `ctxs` is a list of Contexts, one per shard, in this process (the same Context may repeat; each
+    needs the scene uploaded). The shards' slabs are copied to the first context's device and assembled there by
+    rt_assemble[_linear]_async; K_p is merged on the host through `shard_pixel_map`.
+
+    Distributed mode: `ctxs` is one Context and (`rank`, `world`) this process's place in the default
+    torch.distributed group, after ShardedFrame's pattern: with the nccl backend the slabs go through
+    all_gather_into_tensor, with gloo they are staged through the host; counts go through all_reduce; rank 0
+    assembles, and the image-returning calls give None arrays on the other ranks. `gather` forces the
+    collective at world 1.
+
+    Every rank (every shard) must make the same calls in the same order."""
+
+    def __init__(self, ctxs, cam, params, moments: bool = False, *, rank: Optional[int] = None,
+                 world: Optional[int] = None, backend: str = "nccl", gather: Optional[bool] = None, _frames=None):
+        self.local = isinstance(ctxs, (list, tuple))
+        if self.local:
+            self.ctxs, self.world, self.rank = list(ctxs), len(ctxs), 0
+            ranks = list(range(self.world))
+        else:
+            if rank is None or world is None:
+                raise ValueError("distributed mode needs rank and world")
+            self.ctxs, self.world, self.rank = [ctxs], int(world), int(rank)
+            ranks = [self.rank]
+        if self.world < 1:
+            raise ValueError("at least one shard")
+        self.backend = backend
+        self.gather = (not self.local and self.world > 1) if gather is None else bool(gather)
+        if not self.local and self.world > 1 and not self.gather:
+            raise ValueError("a distributed frame of more than one shard needs the gather (rank 0 assembles every slab)")
+        self.p = shard_params(params, 0, self.world)
+        self.width, self.height, self.spp = params.width, params.height, params.spp
+        self.chunk, self.chunks_total = _rt.frame_chunking(self.width * self.height, self.spp)
+        self.tracks_moments = bool(moments)
+        self.frames = _frames if _frames is not None else [
+            c.open_shard_frame(cam, shard_params(params, r, self.world), moments=moments)
+            for c, r in zip(self.ctxs, ranks)]
+        self.chunks_done = max(f.chunks_done for f in self.frames)
+        self.slab_pixels = self.frames[0].slab_pixels
+        self.root = self.ctxs[0]  # (assembles: local mode's first context, or rank 0's)
+        self.active_pixels = self.width * self.height
+
+    @classmethod
+    def restore(cls, ctxs, blob: bytes, moments: Optional[np.ndarray] = None, *, world: Optional[int] = None,
+                rank: Optional[int] = None, backend: str = "nccl", gather: Optional[bool] = None):
+        """The frame a whole-image blob (`save`'s, or ProgressiveFrame.save's) holds, over `world` shards: the
+        shard count of the saved frame does not matter. Local mode: world defaults to len(ctxs)."""
+        info = blob_info(blob)
+        local = isinstance(ctxs, (list, tuple))
+        m = len(ctxs) if local and world is None else world
+        if m is None or (local and m != len(ctxs)):
+            raise ValueError("world must be given (local mode: one context per shard)")
+        pairs = list(zip(ctxs, range(m))) if local else [(ctxs, rank)]
+        frames = [restore_shard_frame(c, blob, r, m, moments) for c, r in pairs]
+        return cls(ctxs, info["camera"], info["params"], moments is not None, rank=rank, world=m, backend=backend,
+                   gather=gather, _frames=frames)
+
+    @property
+    def complete(self) -> bool:
+        return self.chunks_done >= self.chunks_total
+
+    # ---- plumbing
+    def _torch(self):
+        import torch
+        return torch
+
+    def _root_device(self):
+        return f"cuda:{self.root.device}"
+
+    def _all_slabs(self, slabs):
+        """The shards' slabs (this process's, one torch tensor per local frame) as one [world, slab, ...] tensor
+        on the root device; None on a distributed rank other than 0 when nothing is gathered."""
+        torch = self._torch()
+        if self.local:
+            out = torch.zeros((self.world,) + tuple(slabs[0].shape), dtype=slabs[0].dtype, device=self._root_device())
+            for r, t in enumerate(slabs):
+                out[r].copy_(t)  # (device to device, across devices when the contexts differ)
+            return out
+        slab = slabs[0]
+        if not self.gather:
+            return slab.unsqueeze(0)
+        import torch.distributed as dist
+        if self.backend == "nccl":
+            out = torch.zeros((self.world,) + tuple(slab.shape), dtype=slab.dtype, device=slab.device)
+            dist.all_gather_into_tensor(out, slab)
+            return out
+        host = slab.cpu()
+        parts = [torch.empty_like(host) for _ in range(self.world)]
+        dist.all_gather(parts, host)
+        return torch.stack(parts).to(slab.device)
+
+    def _assemble(self, slabs):
+        """[world, slab, 3] uint8 or float64 slabs -> numpy [H, W, 3] on the root (None elsewhere)."""
+        torch = self._torch()
+        if self.rank != 0:
+            return None
+        slabs = slabs.contiguous()
+        img = torch.zeros((self.height, self.width, 3), dtype=slabs.dtype, device=slabs.device)
+        if slabs.dtype == torch.uint8:
+            self.root.assemble_async(self.p, slabs.data_ptr(), img.data_ptr())
+        else:
+            self.root.assemble_linear_async(self.p, slabs.data_ptr(), img.data_ptr())
+        torch.cuda.synchronize(slabs.device)
+        return img.cpu().numpy()
+
+    def _sum_counts(self, dicts, keys) -> dict:
+        """The shards' exact counts added (rt.h: frame and adapt stats merge by plain addition)."""
+        tot = [int(sum(d[k] for d in dicts)) for k in keys]
+        if not self.local and self.world > 1:
+            import torch.distributed as dist
+            torch = self._torch()
+            t = torch.tensor(tot, dtype=torch.int64, device=self._root_device() if self.backend == "nccl" else "cpu")
+            dist.all_reduce(t)
+            tot = [int(x) for x in t.cpu()]
+        return dict(zip(keys, tot))
+
+    def _slabs_of(self, make, fill):
+        ts = []
+        for f in self.frames:
+            t = make(f)
+            fill(f, t)
+            ts.append(t)
+        return ts
+
+    # ---- ProgressiveFrame's surface
+    def advance(self, max_chunks: int = 1) -> int:
+        n = max(f.advance(max_chunks) for f in self.frames)
+        if not self.local and self.world > 1:
+            n = self._max_int(n)
+        self.chunks_done += n
+        return n
+
+    def _max_int(self, n: int) -> int:
+        import torch.distributed as dist
+        torch = self._torch()
+        t = torch.tensor([n], dtype=torch.int64, device=self._root_device() if self.backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return int(t.cpu()[0])
+
+    def resolve(self, rgb: bool = True, linear: bool = True):
+        """(rgb8[H,W,3] | None, linear[H,W,3] | None, stats dict): the shards' previews assembled; nan_pixels and
+        bytes_changed added over the shards, kernel_ms the slowest local shard's."""
+        torch = self._torch()
+        stats, rgbs, lins = [], [], []
+        for f in self.frames:
+            t_rgb = f.slab_tensor(torch.uint8) if rgb else None
+            t_lin = f.slab_tensor(torch.float64) if linear else None
+            stats.append(f.resolve_into(t_rgb, t_lin))
+            rgbs.append(t_rgb)
+            lins.append(t_lin)
+        out = dict(stats[0])
+        out["chunks_done"] = max(s["chunks_done"] for s in stats)
+        out["samples_done"] = max(s["samples_done"] for s in stats)
+        out["kernel_ms"] = max(s["kernel_ms"] for s in stats)
+        out.update(self._sum_counts(stats, ("nan_pixels", "bytes_changed")))
+        img = self._assemble(self._all_slabs(rgbs)) if rgb else None
+        lin = self._assemble(self._all_slabs(lins)) if linear else None
+        return img, lin, out
+
+    def stats(self) -> dict:
+        return self.resolve(rgb=False, linear=False)[2]
+
+    def error(self, abs_tol: float = 0.0, rel_tol: float = 0.0, want_map: bool = True):
+        """(se[H,W,3] | None, stats dict): the shards' error maps assembled, their stats merged by
+        rt_error_stats_merge (a shard whose pixels are all stopped may lag in chunks_done: its stats are
+        per pixel at (K_p, N_p) anyway and are merged at the frame's)."""
+        torch = self._torch()
+        parts, maps = [], []
+        for f in self.frames:
+            t = f.slab_tensor(torch.float64) if want_map else None
+            parts.append(f.error_into(t, abs_tol, rel_tol))
+            maps.append(t)
+        if not self.local and self.world > 1:
+            import torch.distributed as dist
+            row = torch.tensor([float(parts[0][k]) for k in ERROR_FIELDS], dtype=torch.float64,
+                               device=self._root_device() if self.backend == "nccl" else "cpu")
+            rows = [torch.empty_like(row) for _ in range(self.world)]
+            dist.all_gather(rows, row)
+            parts = [{k: (float(v) if k in ("max_se", "mean_se") else int(v)) for k, v in zip(ERROR_FIELDS, r.cpu().tolist())}
+                     for r in rows]
+        k_done = max(p["chunks_done"] for p in parts)
+        n_done = max(p["samples_done"] for p in parts)
+        parts = [dict(p, chunks_done=k_done, samples_done=n_done) for p in parts]
+        se = self._assemble(self._all_slabs(maps)) if want_map else None
+        return se, error_stats_merge(parts)
+
+    def _adapt_merge(self, stats) -> dict:
+        out = self._sum_counts(stats, ("pixels", "active_pixels", "stopped_nan", "stopped_converged_or_masked",
+                                       "stopped_now"))
+        out["chunks_done"] = max(s["chunks_done"] for s in stats)
+        self.active_pixels = out["active_pixels"]
+        return out
+
+    def adapt(self, abs_tol: float = 0.0, rel_tol: float = 0.0, min_chunks: int = 2, nan: bool = True,
+              converged: bool = True) -> dict:
+        return self._adapt_merge([f.adapt(abs_tol, rel_tol, min_chunks, nan, converged) for f in self.frames])
+
+    def stop(self, mask) -> dict:
+        """The same image-order mask[H,W] to every shard (each reads its own pixels)."""
+        return self._adapt_merge([f.stop(mask) for f in self.frames])
+
+    def _merge_host(self, slabs: np.ndarray) -> np.ndarray:
+        """[world, slab] slabs -> [H, W] through shard_pixel_map (the host's statement of the slab layout)."""
+        out = np.zeros(self.height * self.width, dtype=slabs.dtype)
+        for r in range(self.world):
+            m = _rt.shard_pixel_map(shard_params(self.p, r, self.world))
+            ok = m >= 0
+            out[m[ok]] = slabs[r][ok]
+        return out.reshape(self.height, self.width)
+
+    def chunk_counts(self) -> Optional[np.ndarray]:
+        """K_p[H,W] (int32): the shards' slab-order counts merged on the host (None off the root)."""
+        torch = self._torch()
+        ks = self._slabs_of(lambda f: f.slab_tensor(torch.int32, 0), lambda f, t: f.state_into(None, None, t))
+        allk = self._all_slabs(ks)
+        return self._merge_host(allk.cpu().numpy()) if self.rank == 0 else None
+
+    def _state_image(self, which: str) -> Optional[np.ndarray]:
+        torch = self._torch()
+        fill = (lambda f, t: f.state_into(t, None, None)) if which == "sums" else (lambda f, t: f.state_into(None, t, None))
+        return self._assemble(self._all_slabs(self._slabs_of(lambda f: f.slab_tensor(torch.float64), fill)))
+
+    def moments(self) -> Optional[np.ndarray]:
+        """Q[H,W,3] in image order, as ProgressiveFrame.moments."""
+        return self._state_image("moments")
+
+    def save(self):
+        """(blob, moments | None): the whole image's version-1 blob, header (rt_frame_save_header) plus the
+        assembled sums, byte for byte the unsharded frame's `save()`, and with a tracked frame its moments
+        in image order: what `restore` and `Context.restore_frame` take. (None, None) off the root."""
+        head = self.frames[0].save_header()
+        sums = self._state_image("sums")
+        q = self.moments() if self.tracks_moments else None
+        if self.rank != 0:
+            return None, None
+        return head + np.ascontiguousarray(sums, dtype="<f8").tobytes(), q
+
+    def close(self):
+        for f in self.frames:
+            f.close()
+        self.frames = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
