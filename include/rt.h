@@ -820,6 +820,15 @@ int rt_frame_chunking(int64_t pixels, int spp, int* out_chunk, int* out_chunks_t
                               global-memory kernels of spheres-only worlds take */
 int rt_debug_closest_hits(rt_ctx* ctx, const double* rays, int n, double tmin, double tmax,
                           uint64_t seed, uint32_t flags, double* out);
+/*
+ * Debug: how the 4-wide walk orders a node's children (include/rt_wide.h, packed sort keys). out[0] = 1 when
+ * the ctx's last tier-B launch, or its last rt_debug_closest_hits call with RT_DEBUG_WIDE if that came later,
+ * sorted packed keys (0: key / reference pairs, or no 4-wide walk); out[1] = 1 when the uploaded world's
+ * 4-wide tree is within the packed keys' id bound; out[2] = the bits a packed word gives the child
+ * reference; out[3] = the most 4-wide nodes an LDS-staged launch can be given (every such tree is within
+ * the bound). Either form computes the same hits and images.
+ */
+int rt_debug_wide_keys(rt_ctx* ctx, int out[4]);
 
 /*
  * Debug / parity entry: single hot-path functions on the device (golden vectors per function,

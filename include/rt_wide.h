@@ -36,6 +36,42 @@ typedef struct rt_qnode {
   int32_t child[RT_WIDE];
 } rt_qnode;
 
+// ---- packed sort keys (the 4-wide walk's wide_node<F, true>, rt_trace.h)
+// A child's sort key and its reference in one 32-bit word: the fp32 key's top 32 - RT_WKEY_BITS bits (sign,
+// 8 exponent and 9 mantissa bits) over the reference's low RT_WKEY_BITS bits, so that four words sort with
+// integer min / max alone and no child id travels beside its key. The words are compared as SIGNED ints: an
+// accepted key is a non-negative float below +inf (its bit pattern orders as an integer; -0.0, which only the
+// rays the fp32 test cannot describe produce, is the most negative word and sorts first, as the zero it is), a
+// rejected key is +inf exactly, whose word 0x7f800000 | ref lies above every accepted one. The truncation
+// only changes the order among children whose entry distances agree to 2^-9 relative; equal truncated keys
+// fall back to the reference's bits, which is deterministic. The walk's result does not depend on the order.
+// A reference is a wide node id >= 0 or ~leaf slot < 0: both survive the sign-extending unpack while
+// -2^(BITS-1) <= ref < 2^(BITS-1), i.e. for trees of at most RT_WKEY_MAX_IDS wide nodes and as many leaf slots
+// (rt_wkey_fits; the host takes the unpacked form otherwise). An LDS-staged tree always fits: 160 KiB hold
+// fewer than 1280 wide nodes of 128 bytes, and a tree of n wide nodes has at most 4 n leaf slots (< 5120).
+#define RT_WKEY_BITS 14
+#define RT_WKEY_MASK ((1u << RT_WKEY_BITS) - 1u)
+#define RT_WKEY_MAX_IDS (1 << (RT_WKEY_BITS - 1))
+#define RT_WKEY_REJECTED 0x7f800000u  /* +inf: the key of a child whose box the ray misses */
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define RT_WKEY_FN __host__ __device__ static inline
+#else
+#define RT_WKEY_FN static inline
+#endif
+
+RT_WKEY_FN int rt_wkey_fits(long long n_wide_nodes, long long n_leaf_slots) {
+  return n_wide_nodes <= RT_WKEY_MAX_IDS && n_leaf_slots <= RT_WKEY_MAX_IDS;
+}
+// (key_bits: the fp32 key's bit pattern)
+RT_WKEY_FN int32_t rt_wkey_pack(uint32_t key_bits, int32_t ref) {
+  return (int32_t)((key_bits & ~RT_WKEY_MASK) | ((uint32_t)ref & RT_WKEY_MASK));
+}
+RT_WKEY_FN int32_t rt_wkey_ref(int32_t word) {
+  const uint32_t low = (uint32_t)word & RT_WKEY_MASK;  // sign-extend the low RT_WKEY_BITS bits
+  return (int32_t)(low ^ (1u << (RT_WKEY_BITS - 1))) - (1 << (RT_WKEY_BITS - 1));
+}
+
 #ifdef __cplusplus
 static_assert(sizeof(rt_wnode) == 128, "rt_wnode is 128 bytes");
 static_assert(sizeof(rt_qnode) == 64, "rt_qnode is 64 bytes");

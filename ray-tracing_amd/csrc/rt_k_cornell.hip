@@ -5,7 +5,7 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip) {
-  return pick<kVarCornell>(loop, lds, w, count, leaf_lds, false, skip);
+const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip, bool pk) {
+  return pick<kVarCornell>(loop, lds, w, count, leaf_lds, false, skip, pk);
 }
 }  // namespace rt

@@ -452,7 +452,8 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES) render_philox_lds(RenderAr
 // ended and starts their next segment (or sample, or pixel), then steps every walking lane one
 // node at a time until at most trav_stop/64 of the live lanes are still walking. Lanes never
 // wait for the slowest walk of their wave, and shading runs for many lanes at once.
-template <unsigned F>
+// PK: the 4-wide walk sorts a node's children as packed keys (wide_node<F, true>; worlds within rt_wkey_fits).
+template <unsigned F, bool PK = false>
 __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchConst& L, const Scene& S, int* stk,
                                              int stride, int* side_p, volatile uint32_t* wq) {
   const int lane = threadIdx.x & 63;
@@ -653,7 +654,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
     const int live = __popcll(__ballot(true));
     const int stop = (live * A.trav_stop) >> 6;
     const int ls = (F & F_WIDE) ? A.leaf_stop : A.box_first;
-    walk_until<F>(S, t, walking, kEps, stk, stride, joint, stop, (live * ls) >> 6, cnt, g, side, A.med_batch);
+    walk_until<F, PK>(S, t, walking, kEps, stk, stride, joint, stop, (live * ls) >> 6, cnt, g, side, A.med_batch);
     ready = !walking;
     if constexpr ((F & F_COUNT) != 0) {
       const unsigned long long s2 = stamp();
@@ -711,7 +712,9 @@ __global__ void __launch_bounds__(RT_BLOCK, WAVES) render_philox2(RenderArgs A, 
 // LEAF_LDS: the 4-wide walk's leaf table is staged too (n_leaves > 0); as its own instantiation,
 // so that the leaf reads compile to ds_read (a pointer that is LDS or global at run time would
 // make them flat loads, which wait on both the vector-memory and LDS counters).
-template <unsigned F, int WAVES, bool LEAF_LDS = false>
+// PK: packed sort keys in the 4-wide walk (its own instantiation as well, not a flag bit: the flag word is
+// what rt_launch_info reports, and the form changes no result).
+template <unsigned F, int WAVES, bool LEAF_LDS = false, bool PK = false>
 __global__ void __launch_bounds__(WAVES * 256, WAVES)
     render_philox2_lds(RenderArgs A, int n_nodes, int stack_entries, int n_leaves) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds0[];
@@ -745,7 +748,7 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES)
   // (per lane: stack_entries stack entries, then side_ints_of Side slots, then lane_lds_of's 4 lane ints —
   // launch_philox sizes the dynamic LDS with the same helpers)
   int* side_p = reinterpret_cast<int*>(lane_base + (size_t)stack_entries * lanes * sizeof(int)) + threadIdx.x;
-  philox_loop2<F>(A, L, S, stk, lanes, side_p, wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
+  philox_loop2<F, PK>(A, L, S, stk, lanes, side_p, wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
 }
 
 // The tail's work-items (work_unit): each chunk's sample colours added in sample order from 0, as the
@@ -1312,7 +1315,7 @@ __global__ void __launch_bounds__(256) frame_chunk_counts_slab(const int* kp, in
 }
 
 // ---------------------------------------------------------------- debug: closest hits
-template <unsigned F>
+template <unsigned F, bool PK = false>
 __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* rays, int n, double tmin,
                                                          double tmax, uint64_t seed, int joint, int walk, double* out) {
   __shared__ int stk_mem[(lane_ints<F>() + 1) * RT_BLOCK];
@@ -1336,9 +1339,10 @@ __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* 
     if (S.ref_walk) trav_restart_ref(t, S.world, tmax);  // (the re-bounded skeleton, mixed walk)
     trav_media_first<F>(S, t, tmin, cnt, g, side);        // (hoisted media as the render loop takes them)
     bool walking = true;
-    walk_until<F>(S, t, walking, tmin, stk, RT_BLOCK, joint != 0, 0, 0, cnt, g, side);
+    walk_until<F, PK>(S, t, walking, tmin, stk, RT_BLOCK, joint != 0, 0, 0, cnt, g, side);
     if (t.tie || (kRefMixed<F> && t.lite)) {
       trav_redo<F>(t, S.world_ref, tmax);
+      if constexpr (kNoInv<F>) t.ray = prep(plain(t.ray));  // (the redo's binary box tests need 1/d)
       while (trav_step<F>(S, t, tmin, stk, RT_BLOCK, joint != 0, cnt, g, side)) {
       }
     }
@@ -1455,8 +1459,22 @@ __global__ void math_probe(int op, const double* x, const double* y, int n, doub
 // sample per lane walk, 1 = ray replacement over the binary tree, 2 = replacement over the
 // 4-wide tree. `skip`: the F_SKIP instantiation of the same kernel (an adaptive frame's launches; there
 // is no counting build of those).
+// The LDS-staged 4-wide kernels that sort packed keys (worlds within rt_wkey_fits: launch_philox).
 template <unsigned V>
-const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false) {
+const void* pick_packed(int w, bool leaf_lds) {
+  static_assert((V & F_WIDE) != 0, "4-wide kernels only");
+  if (leaf_lds) {
+    if (w == 4) return (const void*)render_philox2_lds<V, 4, true, true>;
+    if (w == 2) return (const void*)render_philox2_lds<V, 2, true, true>;
+    if (w == 3) return (const void*)render_philox2_lds<V, 3, true, true>;
+  }  // (1 wave: the leaves are read from global memory)
+  if (w == 2) return (const void*)render_philox2_lds<V, 2, false, true>;
+  if (w == 4) return (const void*)render_philox2_lds<V, 4, false, true>;
+  if (w == 1) return (const void*)render_philox2_lds<V, 1, false, true>;
+  return (const void*)render_philox2_lds<V, 3, false, true>;
+}
+template <unsigned V>
+const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false, bool pk = false) {
   if constexpr ((V & ~F_SKIP) == (kVarSpheres | F_WIDE)) {
     if (!lds && q) {  // (the quantised tree and sphere quadruples from global memory)
       if (w == 2) return (const void*)render_philox2<V | F_QNODE, 2>;
@@ -1464,6 +1482,10 @@ const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false) {
       if (w == 4) return (const void*)render_philox2<V | F_QNODE, 4>;
       return (const void*)render_philox2<V | F_QNODE, 1>;
     }
+  }
+  // (the spheres-only variant's packed kernels are instantiated in a unit of their own, rt_k_spheres_packed.hip)
+  if constexpr ((V & F_WIDE) != 0 && (V & ~F_SKIP) != (kVarSpheres | F_WIDE)) {
+    if (lds && pk) return pick_packed<V>(w, leaf_lds);
   }
   if constexpr ((V & F_WIDE) != 0) {
     if (lds && leaf_lds) {
@@ -1484,9 +1506,10 @@ const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false) {
   return (const void*)render_philox2<V, 1>;
 }
 template <unsigned V>
-const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = false, bool skip = false) {
+const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = false, bool skip = false,
+                 bool pk = false) {
   if constexpr ((V & F_SKIP) == 0) {
-    if (skip) return count ? nullptr : pick<V | F_SKIP>(loop, lds, w, false, leaf_lds, q);
+    if (skip) return count ? nullptr : pick<V | F_SKIP>(loop, lds, w, false, leaf_lds, q, false, pk);
     if (count) {
       if constexpr (V == kVarSpheres) {
         if (loop == 2 && q) return (const void*)render_philox2<V | F_WIDE | F_COUNT | F_QNODE, 1>;
@@ -1495,7 +1518,7 @@ const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = 
       return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
     }
   }
-  if (loop == 2) return pick_w<V | F_WIDE>(lds, w, leaf_lds, q);
+  if (loop == 2) return pick_w<V | F_WIDE>(lds, w, leaf_lds, q, pk);
   if (loop == 1) return pick_w<V>(lds, w);
   if (lds) {
     if (w == 2) return (const void*)render_philox_lds<V, 2>;
@@ -1529,9 +1552,10 @@ const void* pick_full(int loop, bool lds, int w, bool count, bool skip = false) 
 // Render-kernel tables, one per kernel translation unit: the kernel for (loop, LDS-staged?, waves per
 // SIMD, counting build?, leaf table in LDS?) of that unit's variant(s).
 namespace rt {
-const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q, bool skip);
+const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q, bool skip, bool pk);
 const void* philox_kernel_spheres_global(int w, bool skip);  // rt_k_spheres_global.hip
-const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip);
+const void* philox_kernel_spheres_packed(int w, bool leaf_lds, bool skip);  // rt_k_spheres_packed.hip
+const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip, bool pk);
 const void* philox_kernel_full(int loop, bool lds, int w, bool count, bool skip);
 const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count, bool skip);
 }  // namespace rt

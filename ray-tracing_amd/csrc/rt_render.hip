@@ -77,6 +77,7 @@ struct rt_ctx {
   size_t acc_bytes = 0;
   double last_ms = 0.0;
   rt_launch_info last_launch{};  // rt_last_launch
+  int last_wide_packed = 0;      // the last 4-wide walk sorted packed keys (rt_debug_wide_keys)
   // rt_render's frame events: after the render launches (gather start), after the gather, after assembly
   hipEvent_t ev_gather = nullptr, ev_gathered = nullptr, ev_asm = nullptr;
   rt_frame_timing last_frame{};  // rt_last_frame_timing
@@ -323,20 +324,32 @@ int waves_target(int dflt) {
 }
 // (the render kernels live in one translation unit per variant: rt_k_*.hip)
 // (skip: the F_SKIP instantiation, an adaptive frame's launches)
+// (pk: the LDS-staged 4-wide kernels' packed-key instantiation, wide_keys_packed)
 const void* philox_kernel(unsigned var, int loop, bool lds, int w, bool count, bool skip, bool leaf_lds = false,
-                          bool q = false) {
+                          bool q = false, bool pk = false) {
   if (var == kVarSpheres) {
     // (the 4-wide tree from global memory, 128-byte nodes: its own unit, rt_k_spheres_global.hip)
     if (loop == 2 && !lds && !count && !q && !std::getenv("RTAMD_NO_COLD")) return rt::philox_kernel_spheres_global(w, skip);
-    return rt::philox_kernel_spheres(loop, lds, w, count, leaf_lds, q, skip);
+    return rt::philox_kernel_spheres(loop, lds, w, count, leaf_lds, q, skip, pk);
   }
-  if (var == kVarCornell) return rt::philox_kernel_cornell(loop, lds, w, count, leaf_lds, skip);
+  if (var == kVarCornell) return rt::philox_kernel_cornell(loop, lds, w, count, leaf_lds, skip, pk);
   if (var == kVarFullDark) return rt::philox_kernel_full_dark(loop, lds, w, count, skip);
   return rt::philox_kernel_full(loop, lds, w, count, skip);
 }
 bool env_off(const char* name) {
   const char* e = std::getenv(name);
   return e && e[0] == '0';
+}
+// The largest 4-wide tree an LDS-staged launch can be given: its 128-byte nodes alone within the budget
+// (whatever the waves, stacks and leaf table take comes off that).
+constexpr int kLdsMaxWideNodes = (int)((kLdsBudget - kLcBytes) / sizeof(rt_wnode));
+// Every LDS-staged tree is within the packed sort keys' id bound (include/rt_wide.h), with its at most 4
+// leaf slots per node; wide_keys_packed still checks the uploaded world's own counts.
+static_assert(4 * kLdsMaxWideNodes <= RT_WKEY_MAX_IDS, "an LDS-staged 4-wide tree fits the packed keys");
+// wide_node's packed-key form for this world's 4-wide walks (RTAMD_PACKED_KEYS=0: the key / reference pairs,
+// for A/B runs): the LDS-staged kernels and the closest-hits probe.
+bool wide_keys_packed(const rt_ctx* c) {
+  return c->d_wnodes && rt_wkey_fits(c->n_wnodes, c->n_leaves) && !env_off("RTAMD_PACKED_KEYS");
 }
 template <bool LDS>
 const void* exact_variant_l(unsigned f, bool shared_libm) {
@@ -644,7 +657,9 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
     const int block = waves * 256;
     const size_t bytes = lds_bytes(waves, n_leaves);
     if (bytes <= kLdsBudget) {
-      const void* fn = philox_kernel(var, loop, true, waves, false, skip, n_leaves > 0);
+      const bool pk = wide && wide_keys_packed(c);
+      const void* fn = philox_kernel(var, loop, true, waves, false, skip, n_leaves > 0, false, pk);
+      c->last_wide_packed = pk;
       HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
       int n_items = items;
       void* args[] = {&R, &n_items, (void*)&entries, &n_leaves};
@@ -657,6 +672,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   // (spheres-only worlds uploaded with RTAMD_QNODE=1 read the 4-wide tree from global memory in its
   // 64-byte quantised form: A/B only, measured slower)
   const void* fn = philox_kernel(var, loop, false, count ? 1 : waves, count, skip, false, loop == 2 && c->d_qnodes);
+  c->last_wide_packed = 0;
   // replacement loops: lane stacks (+ Side slots) in dynamic LDS, sized for this world's stack bound
   // (wide_node writes 3 slots)
   int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;
@@ -1236,6 +1252,15 @@ int rt_last_kernel_ms(rt_ctx* c, double* out_ms) {
 int rt_last_launch(rt_ctx* c, rt_launch_info* out) {
   if (!c || !out) return invalid("null argument");
   *out = c->last_launch;
+  return RT_OK;
+}
+
+int rt_debug_wide_keys(rt_ctx* c, int out[4]) {
+  if (!c || !out) return invalid("null argument");
+  out[0] = c->last_wide_packed;
+  out[1] = c->has_scene && c->d_wnodes && rt_wkey_fits(c->n_wnodes, c->n_leaves);
+  out[2] = RT_WKEY_BITS;
+  out[3] = kLdsMaxWideNodes;
   return RT_OK;
 }
 
@@ -1943,10 +1968,18 @@ int rt_debug_closest_hits(rt_ctx* c, const double* rays, int n, double tmin, dou
   if (flags & RT_DEBUG_QNODE)
     hipLaunchKernelGGL(closest_hits<F_UV | F_WIDE | F_QNODE>, grid, dim3(RT_BLOCK), 0, c->stream, c->scene, d_rays, n,
                        tmin, tmax, seed, joint, 1, d_out);
-  else if (flags & RT_DEBUG_WIDE)
-    hipLaunchKernelGGL(closest_hits<F_ALL | F_UV | F_WIDE>, grid, dim3(RT_BLOCK), 0, c->stream, c->scene, d_rays, n,
-                       tmin, tmax, seed, joint, 1, d_out);
-  else
+  else if (flags & RT_DEBUG_WIDE) {
+    // the wide_node form and ray set-up the render kernels of this world run: packed sort keys when the tree
+    // is within their bound, and the spheres-only variant's walk (fp32 reciprocals from the direction)
+    const bool pk = wide_keys_packed(c), sph = variant_for(c->features) == kVarSpheres;
+    const void* fn = sph ? (pk ? (const void*)closest_hits<F_UV | F_WIDE, true> : (const void*)closest_hits<F_UV | F_WIDE>)
+                         : (pk ? (const void*)closest_hits<F_ALL | F_UV | F_WIDE, true>
+                               : (const void*)closest_hits<F_ALL | F_UV | F_WIDE>);
+    int joint_i = joint, walk = 1;
+    void* args[] = {&c->scene, &d_rays, &n, &tmin, &tmax, &seed, &joint_i, &walk, &d_out};
+    HIPCHK(hipLaunchKernel(fn, grid, dim3(RT_BLOCK), args, 0, c->stream));
+    c->last_wide_packed = pk;
+  } else
     hipLaunchKernelGGL(closest_hits<F_ALL | F_UV | F_MIXW>, grid, dim3(RT_BLOCK), 0, c->stream, c->scene, d_rays, n,
                        tmin, tmax, seed, joint, (flags & RT_DEBUG_RESUMABLE) ? 1 : 0, d_out);
   HIPCHK(hipGetLastError());

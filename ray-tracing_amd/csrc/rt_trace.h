@@ -7,6 +7,11 @@ namespace rtd {
 // fp32 ray state (Trav::o32 ...) maintained: the 4-wide walk, or the mixed walk's wide subtrees
 template <unsigned F>
 constexpr bool kRay32 = (F & (F_WIDE | F_MIXW)) != 0;
+// The spheres-only variant's 4-wide kernels: nothing in their walk reads Trav::ray.inv in fp64 (sphere_t does
+// not, and a tie redo computes it when it starts), so a walk begins without prep()'s three fp64 divisions and
+// the fp32 reciprocals come from the direction itself (set_ray32).
+template <unsigned F>
+constexpr bool kNoInv = (F & F_WIDE) != 0 && (F & (F_ALL | F_MIXW)) == 0;
 
 // Work counters of the counting build (F_COUNT); all zero-cost otherwise.
 struct Cnt {
@@ -690,13 +695,30 @@ __device__ __forceinline__ float f32_upper(double x) {  // >= x (or +inf)
 // The ray in fp32 for the conservative child-box test (wide_keys2), from t.ray: the 4-wide walk's
 // rays, and in the mixed walk every ray a frame opens or closes (t.tmax32 is left alone: the bound
 // is in t units, which the instance transforms keep).
+// FROM_D (kNoInv kernels): i32 = 1.0f / fp32(d), the IEEE fp32 division, instead of fp32(RN(1 / d)) — t.ray.inv
+// is not read. It carries two fp32 roundings instead of one (relative error <= 2 eps instead of eps; the proof
+// is at wide_keys2). d = +-0 gives +-inf with d's sign as before; |d| beyond the fp32 range gives 0 as
+// before; a d != 0 whose fp32 value is zero or subnormal (|d| < 2^-126: a subnormal would carry fewer than 24
+// bits into the quotient) is `bad` — before, those with 1/d still finite in fp32 (2^-128 < |d| < 2^-126) were
+// described; now they accept every child, which culls less and decides nothing.
+template <bool FROM_D = false>
 __device__ __forceinline__ void set_ray32(Trav& t, double t_min) {
   t.o32x = (float)t.ray.o.x;
   t.o32y = (float)t.ray.o.y;
   t.o32z = (float)t.ray.o.z;
-  t.i32x = (float)t.ray.inv.x;
-  t.i32y = (float)t.ray.inv.y;
-  t.i32z = (float)t.ray.inv.z;
+  bool tiny = false;
+  if constexpr (FROM_D) {
+    const float dx = (float)t.ray.d.x, dy = (float)t.ray.d.y, dz = (float)t.ray.d.z;
+    t.i32x = 1.0f / dx;
+    t.i32y = 1.0f / dy;
+    t.i32z = 1.0f / dz;
+    tiny = ((fabsf(dx) < 0x1p-126f) & (t.ray.d.x != 0.0)) | ((fabsf(dy) < 0x1p-126f) & (t.ray.d.y != 0.0)) |
+           ((fabsf(dz) < 0x1p-126f) & (t.ray.d.z != 0.0));
+  } else {
+    t.i32x = (float)t.ray.inv.x;
+    t.i32y = (float)t.ray.inv.y;
+    t.i32z = (float)t.ray.inv.z;
+  }
   // K = max |o * (1/d)| over the finite axes (the origin's rounding, in t units)
   const float kx = isinf(t.i32x) ? 0.0f : fabsf(t.o32x * t.i32x);
   const float ky = isinf(t.i32y) ? 0.0f : fabsf(t.o32y * t.i32y);
@@ -709,7 +731,7 @@ __device__ __forceinline__ void set_ray32(Trav& t, double t_min) {
   const bool bad = (isinf(t.i32x) & (t.ray.d.x != 0.0)) | (isinf(t.i32y) & (t.ray.d.y != 0.0)) |
                    (isinf(t.i32z) & (t.ray.d.z != 0.0)) | isnan(t.i32x) | isnan(t.i32y) | isnan(t.i32z) |
                    !isfinite(t.o32x) | !isfinite(t.o32y) | !isfinite(t.o32z) | isnan(t.slack) |
-                   !(t.tmin32 > 0.0f);
+                   !(t.tmin32 > 0.0f) | tiny;
   // A ray with a NaN in its origin or direction (the next segment after a rect hit at t = NaN:
   // trav_take) hits nothing in the reference — its root box test fails (a NaN slab quotient) — and
   // here no child is entered (slack -inf): accepting every child instead walked the whole tree for
@@ -741,7 +763,13 @@ __device__ __forceinline__ void refresh_ray32(Trav& t) {
 
 template <unsigned F>
 __device__ __forceinline__ void trav_begin(Trav& t, const Ray& r, int root, double t_min, double t_max) {
-  t.ray = prep(r);
+  if constexpr (kNoInv<F>) {  // (t.ray.inv stays unset: a tie redo computes it, nothing else reads it)
+    t.ray.o = r.o;
+    t.ray.d = r.d;
+    t.ray.tm = r.tm;
+  } else {
+    t.ray = prep(r);
+  }
   t.closest = t_max;
   t.node = root;
   t.sp = 0;
@@ -756,7 +784,7 @@ __device__ __forceinline__ void trav_begin(Trav& t, const Ray& r, int root, doub
   t.lite = false;
   if constexpr ((F & F_WIDE) != 0) t.node = 0;  // wide root
   if constexpr (kRay32<F>) {
-    set_ray32(t, t_min);
+    set_ray32<kNoInv<F>>(t, t_min);
     t.tmax32 = f32_upper(t_max);
   }
 }
@@ -1049,6 +1077,14 @@ __device__ __forceinline__ void trav_leaf(const Scene& S, Trav& t, const rt_node
 // distances are +-inf (origin outside the slab: near = +inf or far = -inf, rejected; inside:
 // no constraint), or NaN exactly when the origin lies on the plane, which fmaxf/fminf (IEEE
 // maxNum/minNum) drop — the plane then does not constrain, as for a ray inside the slab.
+// With i32 = 1.0f / fp32(d) (set_ray32<true>, the kNoInv kernels) i32 is within 2 eps of 1/d instead of eps,
+// so a plane distance is within eps*(K + 4|t|): the subtraction, the product and i32's two roundings, and
+// eps*K for the origin's (K is computed from the same i32, so it is that i32's |o * i32|). The margins are
+// 2^-21 = 8 eps on each of near and far and 2^-20*K = 16 eps*K of slack; the test's own roundings (near's
+// product, far's fma) take one eps of each, which leaves 7 eps against the 4 eps needed per side and 16
+// eps*K against 2 eps*K (1 + 8 eps): near_c*(1 - 8 eps) <= near*(1 - 4 eps) + eps*K and far_c*(1 + 8 eps) >=
+// far*(1 + 4 eps) - eps*K*(1 + 8 eps) to first order, so an exact near <= far is accepted. The far < 0 case
+// is as above (far <= eps*K).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void wide_keys2(const Trav& t, f32x2 nx, f32x2 ny, f32x2 nz, f32x2 fx, f32x2 fy, f32x2 fz,
@@ -1077,6 +1113,12 @@ __device__ __forceinline__ void cswap(float& ka, int& ca, float& kb, int& cb) {
   ca = c;
 }
 
+__device__ __forceinline__ void pswap(int& a, int& b) {
+  const int lo = min(a, b);
+  b = max(a, b);
+  a = lo;
+}
+
 // The four planes of one axis of a quantised node (rt_qnode): origin + q * scale, exact in fp32.
 __device__ __forceinline__ float4 qplanes(uint32_t q, float s, float o) {
   return float4{fmaf((float)(q & 255u), s, o), fmaf((float)((q >> 8) & 255u), s, o),
@@ -1086,7 +1128,10 @@ __device__ __forceinline__ float4 qplanes(uint32_t q, float s, float o) {
 // One wide node (index `w`): test the four child boxes, enter the nearest accepted child, stack the
 // others (farthest deepest). F_QNODE: the node is read in its quantised form (64 bytes) and its planes
 // decoded; the test over them is the same.
-template <unsigned F = 0>
+// PK: the four children are sorted as packed words (key bits over the child reference, rt_wide.h) by integer
+// min / max instead of as (key, reference) pairs by compare-and-select: no VCC, no v_cndmask, four registers
+// instead of eight across the network. Only for trees within rt_wkey_fits (the host picks the instantiation).
+template <unsigned F = 0, bool PK = false>
 __device__ __forceinline__ bool wide_node(const Scene& S, Trav& t, int* stk, int stride, int w) {
   float4 nx, ny, nz, fx, fy, fz;
   int4 ch;
@@ -1124,11 +1169,26 @@ __device__ __forceinline__ bool wide_node(const Scene& S, Trav& t, int* stk, int
              f32x2{fz.z, fz.w}, k2, k3);
   int c0 = ch.x, c1 = ch.y, c2 = ch.z, c3 = ch.w;
   const int n_hit = (k0 < INFINITY) + (k1 < INFINITY) + (k2 < INFINITY) + (k3 < INFINITY);
-  cswap(k0, c0, k1, c1);
-  cswap(k2, c2, k3, c3);
-  cswap(k0, c0, k2, c2);
-  cswap(k1, c1, k3, c3);
-  cswap(k1, c1, k2, c2);
+  if constexpr (PK) {
+    // (the same 5-exchange network over the packed words, compared as signed ints: rt_wide.h)
+    int p0 = rt_wkey_pack(__float_as_uint(k0), c0), p1 = rt_wkey_pack(__float_as_uint(k1), c1);
+    int p2 = rt_wkey_pack(__float_as_uint(k2), c2), p3 = rt_wkey_pack(__float_as_uint(k3), c3);
+    pswap(p0, p1);
+    pswap(p2, p3);
+    pswap(p0, p2);
+    pswap(p1, p3);
+    pswap(p1, p2);
+    c0 = rt_wkey_ref(p0);
+    c1 = rt_wkey_ref(p1);
+    c2 = rt_wkey_ref(p2);
+    c3 = rt_wkey_ref(p3);
+  } else {
+    cswap(k0, c0, k1, c1);
+    cswap(k2, c2, k3, c3);
+    cswap(k0, c0, k2, c2);
+    cswap(k1, c1, k3, c3);
+    cswap(k1, c1, k2, c2);
+  }
   // Stack the accepted children after c0 without branches, farthest deepest: three slots are always
   // written (slots at or above the new sp are dead; the stacks have 3 entries of headroom for this).
   const int e0 = n_hit > 3 ? c3 : (n_hit > 2 ? c2 : c1);
@@ -1324,10 +1384,10 @@ __device__ __forceinline__ void trav_postpone(Trav& t, int* stk, int stride) {
     t.node = trav_pop(t, stk, stride);
   }
 }
-template <unsigned F>
+template <unsigned F, bool PK = false>
 __device__ __forceinline__ void wide_inner(const Scene& S, Trav& t, int* stk, int stride, Cnt& cnt) {
   if constexpr ((F & F_COUNT) != 0) ++cnt.wide;
-  if (!wide_node<F>(S, t, stk, stride, t.node)) t.node = trav_pop(t, stk, stride);
+  if (!wide_node<F, PK>(S, t, stk, stride, t.node)) t.node = trav_pop(t, stk, stride);
   trav_postpone(t, stk, stride);
 }
 template <unsigned F, class R>
@@ -1348,8 +1408,9 @@ __device__ __forceinline__ void wide_leaf(const Scene& S, Trav& t, double t_min,
 // the walking lanes are at BVH nodes, a step runs only those (lanes at leaves, instances and media
 // wait), so that one step runs the box test alone instead of every node kind its lanes are at
 // (leaf_stop >= the live lanes: every step runs every lane). 4-wide walks: wide-node steps until at
-// most `leaf_stop` walking lanes still look for their first leaf, then one leaf step.
-template <unsigned F, class R>
+// most `leaf_stop` walking lanes still look for their first leaf, then one leaf step (PK: wide_node's
+// packed-key form).
+template <unsigned F, bool PK = false, class R>
 __device__ __forceinline__ void walk_until(const Scene& S, Trav& t, bool& walking, double t_min, int* stk, int stride,
                                            bool joint, int stop, int leaf_stop, Cnt& cnt, R& g, Side& side,
                                            int med_batch = 0) {
@@ -1437,7 +1498,7 @@ __device__ __forceinline__ void walk_until(const Scene& S, Trav& t, bool& walkin
         if (walking && t.ref) {
           walking = trav_step<F>(S, t, t_min, stk, stride, joint, cnt, g, side);
         } else if (walking && t.node >= 0) {
-          wide_inner<F>(S, t, stk, stride, cnt);
+          wide_inner<F, PK>(S, t, stk, stride, cnt);
           walking = t.node != kNone || t.pend >= 0;
         }
       } else {

@@ -185,7 +185,7 @@ EXPORTED = [
     "rt_frame_open_ex", "rt_frame_moments", "rt_frame_restore_ex", "rt_frame_error", "rt_error_estimate",
     "rt_frame_adapt", "rt_frame_stop", "rt_frame_chunk_counts", "rt_adapt_decide",
     "rt_frame_open_shard", "rt_frame_resolve_shard", "rt_frame_error_shard", "rt_error_stats_merge",
-    "rt_frame_shard_state", "rt_frame_save_header", "rt_frame_restore_shard",
+    "rt_frame_shard_state", "rt_frame_save_header", "rt_frame_restore_shard", "rt_debug_wide_keys",
 ]
 
 # include/rt_wide.h: one 4-wide node (128 B)
@@ -266,6 +266,7 @@ def lib() -> C.CDLL:
             "rt_quantize_wide": (I, [C.c_void_p, I, C.c_void_p]),
             "rt_tree_stack_need": (I, [P(rt_node), I, I, P(I)]),
             "rt_last_launch": (I, [C.c_void_p, P(rt_launch_info)]),
+            "rt_debug_wide_keys": (I, [C.c_void_p, P(I)]),
             "rt_write_pfm": (I, [P(D), I, I, I, C.c_char_p, C.c_size_t, P(C.c_size_t)]),
             "rt_debug_probe": (I, [C.c_void_p, P(rt_camera), I, P(D), I, U64, P(D)]),
             "rt_prepare_scene": (I, [P(rt_scene_desc), C.c_uint32, P(rt_scene_info)]),
@@ -746,6 +747,13 @@ class Context:
         info = rt_launch_info()
         _check(lib().rt_last_launch(self._h, C.byref(info)), "rt_last_launch")
         return {k: getattr(info, k) for k, _ in rt_launch_info._fields_}
+
+    def wide_keys(self) -> dict:
+        """rt_debug_wide_keys: whether the last 4-wide walk sorted packed keys, whether the uploaded world is
+        within their id bound, the reference bits of a packed word, the most 4-wide nodes LDS staging holds."""
+        out = (C.c_int * 4)()
+        _check(lib().rt_debug_wide_keys(self._h, out), "rt_debug_wide_keys")
+        return {"packed": out[0], "fits": out[1], "ref_bits": out[2], "lds_max_wide_nodes": out[3]}
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double(0)
