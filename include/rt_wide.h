@@ -72,6 +72,36 @@ RT_WKEY_FN int32_t rt_wkey_ref(int32_t word) {
   return (int32_t)(low ^ (1u << (RT_WKEY_BITS - 1))) - (1 << (RT_WKEY_BITS - 1));
 }
 
+// ---- the stack cull (the packed form's stack holds the sorted words, not the unpacked references: rt_trace.h,
+// wide_node<F, true> pushes them, trav_pop<true> unpacks one, wide_leaf<F, true> culls)
+// A stacked child was accepted under the bound that held when its node was visited. Once a leaf is hit the
+// bound (Trav::tmax32) shrinks, and an entry whose box the ray enters beyond the new bound can be dropped from
+// the stack before it costs a wide step or an fp64 leaf test. The word's key is bits(word & ~RT_WKEY_MASK)
+// read as a float; the entry is beyond the bound exactly when
+//     key * (1 - 2^-21) > fma(tmax32, 1 + 2^-21, slack)
+// — wide_keys2's acceptance (rt_trace.h) with near = key and far = tmax32, negated, the same expression with
+// the same roundings. No new proof is needed:
+//   - the truncated key is <= the true near distance n the word was packed from (truncating the low mantissa
+//     bits of a non-negative float lowers it or leaves it; the accepted key min(n, 3.0e38) is <= n; -0.0 stays);
+//   - fp32 multiplication by a positive constant and the fma (in its first argument, under a positive factor)
+//     are monotone, roundings included;
+//   - a re-test of the child now would use far = min(far planes, tmax32) <= tmax32;
+//   - so "beyond" implies n * (1 - 2^-21) > fma(far, 1 + 2^-21, slack): wide_keys2 itself would reject that
+//     child under the current bound;
+//   - and a box wide_keys2 rejects holds no hit in [tmin, closest_up], a tie at `closest` included, since
+//     tmax32 = f32_upper(closest) >= closest_up.
+// Special cases: tmax32 = +inf (no hit yet) never culls (the right side is +inf, or NaN with slack = -inf);
+// slack = +inf (the rays the fp32 test cannot describe, the only ones with -0.0 keys) never culls (the right
+// side is +inf); the -0.0 word is beyond no bound of tmax32 >= 0 and slack >= 0 either; slack = -inf (NaN rays)
+// has nothing stacked, every child being rejected; tmax32 = 0 after a rect hit at t = NaN leaves `slack` alone
+// as the bound and culls as the box test would, which rejects the same children. A NaN bound culls nothing.
+RT_WKEY_FN int rt_wkey_beyond(int32_t word, float tmax32, float slack) {
+  const uint32_t kb = (uint32_t)word & ~RT_WKEY_MASK;
+  float key;
+  __builtin_memcpy(&key, &kb, sizeof key);  // (the bit pattern as a float, in C and on the device alike)
+  return key * (1.0f - 0x1p-21f) > __builtin_fmaf(tmax32, 1.0f + 0x1p-21f, slack);
+}
+
 #ifdef __cplusplus
 static_assert(sizeof(rt_wnode) == 128, "rt_wnode is 128 bytes");
 static_assert(sizeof(rt_qnode) == 64, "rt_qnode is 64 bytes");

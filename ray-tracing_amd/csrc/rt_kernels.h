@@ -706,6 +706,21 @@ __global__ void __launch_bounds__(RT_BLOCK, WAVES) render_philox2(RenderArgs A, 
                   wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
 }
 
+// The counting build of a 4-wide world whose timed launch takes the packed form (launch_philox): the same
+// global-memory loop with wide_node<F, true> and the stack cull, so that the work counters describe the walk the
+// timed kernel does. A kernel of its own (rt_k_count_packed.hip), so that no timed kernel's name or unit changes.
+template <unsigned F>
+__global__ void __launch_bounds__(RT_BLOCK, 1) render_philox2_count_packed(RenderArgs A, int stack_entries) {
+  static_assert((F & F_WIDE) != 0 && (F & F_COUNT) != 0, "the 4-wide counting build only");
+  extern __shared__ __attribute__((aligned(16))) int stk_mem[];  // (as render_philox2)
+  __shared__ uint32_t wave_q[RT_BLOCK / 64][2];
+  const LaunchConst& L = stage_const(A, stk_mem);
+  __syncthreads();
+  int* lane0 = &stk_mem[kLcBytes / 4 + threadIdx.x];
+  philox_loop2<F, true>(A, L, A.S, lane0, RT_BLOCK, lane0 + stack_entries * RT_BLOCK,
+                        wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
+}
+
 // LDS-staged replacement loop: the traversal's node array (the wide records for F_WIDE, else the
 // flat nodes) and the per-lane stacks live in the CU's LDS; leaves are read from global memory
 // under F_WIDE.
@@ -1555,6 +1570,7 @@ namespace rt {
 const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q, bool skip, bool pk);
 const void* philox_kernel_spheres_global(int w, bool skip);  // rt_k_spheres_global.hip
 const void* philox_kernel_spheres_packed(int w, bool leaf_lds, bool skip);  // rt_k_spheres_packed.hip
+const void* philox_kernel_count_packed(unsigned var);  // rt_k_count_packed.hip (kVarSpheres or kVarCornell)
 const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip, bool pk);
 const void* philox_kernel_full(int loop, bool lds, int w, bool count, bool skip);
 const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count, bool skip);

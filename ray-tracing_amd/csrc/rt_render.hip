@@ -347,7 +347,7 @@ constexpr int kLdsMaxWideNodes = (int)((kLdsBudget - kLcBytes) / sizeof(rt_wnode
 // leaf slots per node; wide_keys_packed still checks the uploaded world's own counts.
 static_assert(4 * kLdsMaxWideNodes <= RT_WKEY_MAX_IDS, "an LDS-staged 4-wide tree fits the packed keys");
 // wide_node's packed-key form for this world's 4-wide walks (RTAMD_PACKED_KEYS=0: the key / reference pairs,
-// for A/B runs): the LDS-staged kernels and the closest-hits probe.
+// for A/B runs): the LDS-staged kernels, the counting build of a world they render, and the closest-hits probe.
 bool wide_keys_packed(const rt_ctx* c) {
   return c->d_wnodes && rt_wkey_fits(c->n_wnodes, c->n_leaves) && !env_off("RTAMD_PACKED_KEYS");
 }
@@ -636,7 +636,10 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   const int side_ints = side_ints_of(var, c->scene.frames, loop) + (lane_lds_of(var, loop) ? 4 : 0);
   // LDS-staged kernel when the traversal's node array plus the stacks fit one CU's 160 KiB
   // (RTAMD_LDS=0 disables it for A/B runs).
-  if (!count && !env_off("RTAMD_LDS") && (!is_full(var) || loop)) {
+  // (the counting build walks from global memory; it only learns here whether the timed launch of this world
+  // takes the packed 4-wide kernels, whose walk it then counts: count_pk)
+  bool count_pk = false;
+  if (!env_off("RTAMD_LDS") && (!is_full(var) || loop)) {
     const int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;  // (wide_node writes 3 slots)
     const int items = wide ? c->n_wnodes : c->n_nodes;
     const size_t rec = wide ? sizeof(rt_wnode) : sizeof(rt_node);
@@ -656,7 +659,9 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
       waves = 4;
     const int block = waves * 256;
     const size_t bytes = lds_bytes(waves, n_leaves);
-    if (bytes <= kLdsBudget) {
+    if (count) {
+      count_pk = bytes <= kLdsBudget && wide && wide_keys_packed(c);
+    } else if (bytes <= kLdsBudget) {
       const bool pk = wide && wide_keys_packed(c);
       const void* fn = philox_kernel(var, loop, true, waves, false, skip, n_leaves > 0, false, pk);
       c->last_wide_packed = pk;
@@ -671,8 +676,9 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
   }
   // (spheres-only worlds uploaded with RTAMD_QNODE=1 read the 4-wide tree from global memory in its
   // 64-byte quantised form: A/B only, measured slower)
-  const void* fn = philox_kernel(var, loop, false, count ? 1 : waves, count, skip, false, loop == 2 && c->d_qnodes);
-  c->last_wide_packed = 0;
+  const void* fn = count_pk ? rt::philox_kernel_count_packed(var)
+                            : philox_kernel(var, loop, false, count ? 1 : waves, count, skip, false, loop == 2 && c->d_qnodes);
+  c->last_wide_packed = count_pk;
   // replacement loops: lane stacks (+ Side slots) in dynamic LDS, sized for this world's stack bound
   // (wide_node writes 3 slots)
   int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;

@@ -828,6 +828,10 @@ __device__ __forceinline__ void trav_restart_ref(Trav& t, int root, double t_max
 // random t) or a rect hit at t = NaN (trav_take) is redone in full.
 // (Kernels for media-free worlds, where ties are rare — C2 none, C3 0.015 per sample — redo in full:
 // the lighter redo's extra state cost the 4-wave spheres kernel 3.5 %.)
+// (A 4-wide walk in the packed form leaves packed words on the lane's LDS stack; the redo's binary steps push
+// and pop plain ids on the same stack. They never meet a word: the redo starts at t.sp = 0 with t.ref set,
+// walk_until and the closest-hits probe step a t.ref lane with trav_step alone, whose binary branch pops only
+// what it pushed since the reset, and the next 4-wide walk starts from trav_begin's t.sp = 0 with t.ref clear.)
 template <unsigned F>
 __device__ __forceinline__ void trav_redo(Trav& t, int root, double t_max) {
   if constexpr (!kRefMixed<F>) {
@@ -1178,10 +1182,16 @@ __device__ __forceinline__ bool wide_node(const Scene& S, Trav& t, int* stk, int
     pswap(p0, p2);
     pswap(p1, p3);
     pswap(p1, p2);
+    // The stack takes the sorted WORDS, entry distance included, so that a leaf hit can drop the entries that
+    // lie beyond its bound (wide_leaf<F, true>, rt_wkey_beyond); only the entered child is unpacked here, a
+    // stacked one where it is popped (trav_pop<true>).
+    // The three-slot push is the one below. A rejected child's word (key +inf) may land in a slot at or above
+    // the new sp, as its id does in the pairs form: a pop reads only below sp, and the next push writes from sp
+    // upwards before sp moves past a slot, so a slot below sp always holds an entry that a push accepted.
     c0 = rt_wkey_ref(p0);
-    c1 = rt_wkey_ref(p1);
-    c2 = rt_wkey_ref(p2);
-    c3 = rt_wkey_ref(p3);
+    c1 = p1;
+    c2 = p2;
+    c3 = p3;
   } else {
     cswap(k0, c0, k1, c1);
     cswap(k2, c2, k3, c3);
@@ -1374,33 +1384,56 @@ __device__ __forceinline__ bool trav_step(const Scene& S, Trav& t, double t_min,
 // step. Culling is looser while a leaf waits (its hit does not yet bound the walk); the closest
 // hit and the tie flag do not depend on the order leaves are tested in (trav_take).
 
+// PK: the stack holds wide_node<F, true>'s packed words; the pop unpacks the reference.
+template <bool PK = false>
 __device__ __forceinline__ int trav_pop(Trav& t, const int* stk, int stride) {
-  return t.sp ? stk[(--t.sp) * stride] : kNone;
+  if constexpr (PK) {
+    return t.sp ? rt_wkey_ref(stk[(--t.sp) * stride]) : kNone;
+  } else {
+    return t.sp ? stk[(--t.sp) * stride] : kNone;
+  }
 }
 // node -> pend when node is a leaf and the slot is free, then continue with the next stack entry
+template <bool PK = false>
 __device__ __forceinline__ void trav_postpone(Trav& t, int* stk, int stride) {
   if (t.node < 0 && t.node != kNone && t.pend < 0) {
     t.pend = ~t.node;
-    t.node = trav_pop(t, stk, stride);
+    t.node = trav_pop<PK>(t, stk, stride);
   }
 }
 template <unsigned F, bool PK = false>
 __device__ __forceinline__ void wide_inner(const Scene& S, Trav& t, int* stk, int stride, Cnt& cnt) {
   if constexpr ((F & F_COUNT) != 0) ++cnt.wide;
-  if (!wide_node<F, PK>(S, t, stk, stride, t.node)) t.node = trav_pop(t, stk, stride);
-  trav_postpone(t, stk, stride);
+  if (!wide_node<F, PK>(S, t, stk, stride, t.node)) t.node = trav_pop<PK>(t, stk, stride);
+  trav_postpone<PK>(t, stk, stride);
 }
-template <unsigned F, class R>
+template <unsigned F, bool PK = false, class R>
 __device__ __forceinline__ void wide_leaf(const Scene& S, Trav& t, double t_min, int* stk, int stride, Cnt& cnt, R& g,
                                           Side& side) {
   // (a loop of at most one trip, not an `if`: as an `if` the 4-wide kernels compile one instruction shorter
   // and differently scheduled, which has not been measured; this form keeps them as they were timed)
   for (int k = 0; k < 1 && t.pend >= 0; ++k) {
     const rt_node* n = &S.leaves[t.pend];  // (pend holds the leaf table slot)
+    [[maybe_unused]] const float bound_before = t.tmax32;
     trav_leaf<F>(S, t, n, t.pend | kSlotTag, t_min, cnt, g, side, false);
     t.pend = -1;
+    if constexpr (PK && (F & F_RECT) == 0) {
+      // The stack cull (rt_wkey_beyond, rt_wide.h). An entry was accepted under the bound of its push; the hit
+      // just taken may have brought t.tmax32 below its entry distance, and the box test would reject it now.
+      // The entries on top of the stack that lie beyond the new bound go here, at once, instead of each costing
+      // a wide step whose four children all fail, or a parked leaf and its fp64 test. Here and not at the pop:
+      // the bound only moves in a leaf step, so the wide step's pops stay a load and an unpack (a test at every
+      // pop, looping or over the top two words, made C2 slower: DESIGN.md 3.1). The sweep stops at the first
+      // entry it keeps; a stale one below it is visited as before, which costs a step and never a hit. The
+      // bound is computed from t.tmax32 and t.slack as they stand; Trav carries nothing new. Sphere-only kernels
+      // alone sweep: in the Cornell-like packed kernels (F_RECT) the sweep cost registers (the 3-wave kernel 12 ->
+      // 48 B/lane of scratch) and 0.8 % on the Cornell box, whose enclosed rays leave little stale; there the
+      // words are stacked and popped, and nothing is dropped.
+      if (t.tmax32 < bound_before)
+        while (t.sp && rt_wkey_beyond(stk[(t.sp - 1) * stride], t.tmax32, t.slack)) --t.sp;
+    }
   }
-  trav_postpone(t, stk, stride);
+  trav_postpone<PK>(t, stk, stride);
 }
 
 // Step the wave's walking lanes until at most `stop` of them still walk (`walking` goes false when
@@ -1507,7 +1540,7 @@ __device__ __forceinline__ void walk_until(const Scene& S, Trav& t, bool& walkin
           kinds = K_LEAF;
         }
         if (holding) {
-          wide_leaf<F>(S, t, t_min, stk, stride, cnt, g, side);
+          wide_leaf<F, PK>(S, t, t_min, stk, stride, cnt, g, side);
           walking = t.node != kNone || t.pend >= 0;
         }
       }
