@@ -102,6 +102,44 @@ RT_WKEY_FN int rt_wkey_beyond(int32_t word, float tmax32, float slack) {
   return key * (1.0f - 0x1p-21f) > __builtin_fmaf(tmax32, 1.0f + 0x1p-21f, slack);
 }
 
+// ---- the lean step loop's lane state (the sphere-only packed kernels' walk_until and wide_leaf, rt_trace.h)
+// A lane of the 4-wide walk with one postponed leaf is described by Trav's node, pend and sp alone, and the step
+// loop reads its predicates off those registers where it uses them instead of carrying a flag per lane:
+//   walking: the walk is not over — a node is left to visit, or a parked leaf to test;
+//   seeking: the slot is free and the lane is at a wide node — it needs wide steps before it can test a leaf;
+//   holding: a leaf is parked — a leaf step tests it.
+// The loop makes progress because every walking lane is seeking or holding: the pops never leave a lane at a leaf
+// with the slot free (trav_postpone parks it), where neither kind of step would move it and its wave would spin.
+// tests/c/walk_step_check.c proves that over every state a step can leave.
+#define RT_WNONE ((int32_t)0x80000000) /* Trav::node once nothing is left to visit (kNone, rt_trace.h) */
+
+RT_WKEY_FN int rt_wlane_walking(int32_t node, int32_t pend) { return (node != RT_WNONE) | (pend >= 0); }
+RT_WKEY_FN int rt_wlane_seeking(int32_t node, int32_t pend) { return (pend < 0) & (node >= 0); }
+RT_WKEY_FN int rt_wlane_holding(int32_t pend) { return pend >= 0; }
+
+typedef struct rt_wstep {
+  int32_t node, pend, sp;  // the lane's Trav::node, Trav::pend (a leaf slot, or -1: free) and Trav::sp
+} rt_wstep;
+
+// The slot of the lane's stack that holds its top entry, or slot 0 of an empty stack (always allocated; what it
+// holds is then ignored): a top-of-stack read needs no branch on sp, and its address is formed from the live
+// stack base (written as stk[(sp - 1) * stride] under `sp != 0`, the compiler hoists the loop-invariant
+// stk - stride out of the walk loop and spills it).
+RT_WKEY_FN int32_t rt_wstep_slot(int32_t sp) { return sp > 0 ? sp - 1 : 0; }
+
+// trav_postpone (rt_trace.h) as selects, for the end of a leaf step: a lane at a leaf with the slot free parks the
+// leaf and goes on with the top entry (`word`, read from slot rt_wstep_slot(sp) by every lane), or with RT_WNONE
+// from an empty stack. The entry taken stays the node whatever it is: the slot is busy now.
+RT_WKEY_FN rt_wstep rt_wstep_postpone(int32_t node, int32_t pend, int32_t sp, int32_t word) {
+  const int park = (node < 0) & (node != RT_WNONE) & (pend < 0);
+  const int has = sp > 0;
+  rt_wstep s;
+  s.node = park ? (has ? rt_wkey_ref(word) : RT_WNONE) : node;
+  s.pend = park ? ~node : pend;
+  s.sp = sp - (park & has);
+  return s;
+}
+
 #ifdef __cplusplus
 static_assert(sizeof(rt_wnode) == 128, "rt_wnode is 128 bytes");
 static_assert(sizeof(rt_qnode) == 64, "rt_qnode is 64 bytes");

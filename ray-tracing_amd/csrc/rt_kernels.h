@@ -525,13 +525,22 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
     // box top's plane, whose pdf is 0 / 0: DESIGN.md §4.3. A walking path's throughput is never NaN in
     // every channel: such a path ends where it is shaded, below.)
     if (ready && (t.tie || (kRefMixed<F> && t.lite)) && !t.redo) {
-      ready = false;
       if constexpr ((F & F_COUNT) != 0) ++cnt.ties;
       trav_redo<F>(t, L.S.world_ref, INFINITY);
       // (the redo's binary box tests need 1/d: recomputed here, the same values, so that the 4-wide
       // walk need not carry Trav::ray.inv)
       if constexpr ((F & F_WIDE) != 0) t.ray = prep(plain(t.ray));
-      walking = true;
+      if constexpr (kLeanWalk<F, PK>) {
+        // The redo runs to its end here, a divergent loop over the flagged lanes, and the lane is shaded below
+        // in this same iteration (`ready` stays set; t.redo keeps it from being redone): the 4-wide step loop then
+        // holds no binary step and no lane in a redo. Ties are rare (C2 none); only test worlds have many.
+        while (trav_step<F, true>(S, t, kEps, stk, stride, joint, cnt, g, side)) {
+        }
+        t.node = kNone;  // (with pend = -1: the walk is over, in walk_until's terms too)
+      } else {
+        ready = false;
+        walking = true;
+      }
     }
     // the next walk's ray: a scattered ray (next segment) or a camera ray (next sample), parked in
     // t.ray (free once the walk's hit is recorded); both kinds of lane start their walk together

@@ -830,8 +830,9 @@ __device__ __forceinline__ void trav_restart_ref(Trav& t, int root, double t_max
 // the lighter redo's extra state cost the 4-wave spheres kernel 3.5 %.)
 // (A 4-wide walk in the packed form leaves packed words on the lane's LDS stack; the redo's binary steps push
 // and pop plain ids on the same stack. They never meet a word: the redo starts at t.sp = 0 with t.ref set,
-// walk_until and the closest-hits probe step a t.ref lane with trav_step alone, whose binary branch pops only
-// what it pushed since the reset, and the next 4-wide walk starts from trav_begin's t.sp = 0 with t.ref clear.)
+// walk_until, philox_loop2 (the lean kernels' redo loop) and the closest-hits probe step a t.ref lane with
+// trav_step alone, whose binary branch pops only what it pushed since the reset, and the next 4-wide walk starts
+// from trav_begin's t.sp = 0 with t.ref clear.)
 template <unsigned F>
 __device__ __forceinline__ void trav_redo(Trav& t, int root, double t_max) {
   if constexpr (!kRefMixed<F>) {
@@ -1247,11 +1248,12 @@ __device__ __forceinline__ bool trav_pop_mixed(const Scene& S, Trav& t, const in
 // (Translate/Rotate over a BVH, Lib.hs:1029-1052): a tagged stack entry, the frame's id in the
 // lane's Side slots, and the child's ray in Trav::ray; when the entry is popped the parent's ray is
 // rebuilt from the world ray through the frames still open (the same operations as on entry).
-template <unsigned F, class R>
+// REDO: the caller steps a tie redo only (t.ref set), so a 4-wide kernel's copy holds the binary step alone.
+template <unsigned F, bool REDO = false, class R>
 __device__ __forceinline__ bool trav_step(const Scene& S, Trav& t, double t_min, int* stk, int stride, bool joint,
                                           Cnt& cnt, R& g, Side& side) {
   bool wide = false;
-  if constexpr ((F & F_WIDE) != 0) wide = !t.ref;
+  if constexpr ((F & F_WIDE) != 0 && !REDO) wide = !t.ref;
   if (wide) {
     if (t.node >= 0) {
       if constexpr ((F & F_COUNT) != 0) ++cnt.wide;
@@ -1401,6 +1403,14 @@ __device__ __forceinline__ void trav_postpone(Trav& t, int* stk, int stride) {
     t.node = trav_pop<PK>(t, stk, stride);
   }
 }
+static_assert(RT_WNONE == kNone, "rt_wide.h's end-of-walk node is Trav's");
+// The sphere-only packed kernels (configs 1 and 2 and their counting build) walk in the lean form: the lane
+// predicates of walk_until read off Trav's registers (rt_wlane_*, rt_wide.h), the tie redo run where it is set up
+// (philox_loop2, rt_kernels.h), and the leaf step's sweep and postpone addressed from the live stack base, without
+// branches on sp. The pairs form and the Cornell-like packed kernels keep the code they were timed with.
+template <unsigned F, bool PK>
+constexpr bool kLeanWalk = PK && (F & F_WIDE) != 0 && (F & F_RECT) == 0;
+
 template <unsigned F, bool PK = false>
 __device__ __forceinline__ void wide_inner(const Scene& S, Trav& t, int* stk, int stride, Cnt& cnt) {
   if constexpr ((F & F_COUNT) != 0) ++cnt.wide;
@@ -1429,11 +1439,30 @@ __device__ __forceinline__ void wide_leaf(const Scene& S, Trav& t, double t_min,
       // alone sweep: in the Cornell-like packed kernels (F_RECT) the sweep cost registers (the 3-wave kernel 12 ->
       // 48 B/lane of scratch) and 0.8 % on the Cornell box, whose enclosed rays leave little stale; there the
       // words are stacked and popped, and nothing is dropped.
-      if (t.tmax32 < bound_before)
-        while (t.sp && rt_wkey_beyond(stk[(t.sp - 1) * stride], t.tmax32, t.slack)) --t.sp;
+      // (The top entry is addressed as slot rt_wstep_slot(sp) from the live stack base and read before sp is
+      // tested: written as stk[(sp - 1) * stride] under `sp != 0` the compiler hoisted the loop-invariant
+      // stk - stride out of the walk loop and spilled it, a scratch reload and a vmcnt wait in every leaf step that
+      // lowered the bound.)
+      if (t.tmax32 < bound_before) {
+        for (;;) {
+          const int top = rt_wstep_slot(t.sp);
+          const int word = stk[top * stride];
+          if (!((t.sp > 0) & (rt_wkey_beyond(word, t.tmax32, t.slack) != 0))) break;
+          t.sp = top;
+        }
+      }
     }
   }
-  trav_postpone<PK>(t, stk, stride);
+  if constexpr (kLeanWalk<F, PK>) {
+    // trav_postpone as selects (rt_wstep_postpone, rt_wide.h): the top word is read by every lane, from slot 0 of an
+    // empty stack, and taken by the lanes at a leaf.
+    const rt_wstep s = rt_wstep_postpone(t.node, t.pend, t.sp, stk[rt_wstep_slot(t.sp) * stride]);
+    t.node = s.node;
+    t.pend = s.pend;
+    t.sp = s.sp;
+  } else {
+    trav_postpone<PK>(t, stk, stride);
+  }
 }
 
 // Step the wave's walking lanes until at most `stop` of them still walk (`walking` goes false when
@@ -1513,6 +1542,43 @@ __device__ __forceinline__ void walk_until(const Scene& S, Trav& t, bool& walkin
         }
       }
     }
+  } else if constexpr (kLeanWalk<F, PK>) {
+    // The lean form. No lane is in a tie redo here (the callers run a redo to its end where they set it up), so a
+    // lane's state is Trav's node, pend and sp alone and the predicates are read off them where they are used,
+    // instead of a bool per lane carried through the loop's phis and turned back into masks every step
+    // (rt_wlane_walking / _seeking / _holding, rt_wide.h). Every walking lane is seeking or holding (wide_inner and
+    // wide_leaf never leave a lane at a leaf with a free slot: tests/c/walk_step_check.c), so one of the two steps
+    // always makes progress. A wide step runs every lane at a wide node, a holding one included; a leaf step every
+    // holding lane. With the binary step out of its body (432 instructions, never run on config 2) this loop is
+    // what the 4-wave kernel's time follows: config 2 90.3 -> 85.3 ms.
+    for (;;) {
+      if (__popcll(__ballot(rt_wlane_walking(t.node, t.pend))) <= stop) break;
+      unsigned kinds = 0;
+      unsigned long long t0 = 0;
+      if constexpr ((F & F_COUNT) != 0) t0 = stamp();
+      if (__popcll(__ballot(rt_wlane_seeking(t.node, t.pend))) > leaf_stop ||
+          __ballot(rt_wlane_holding(t.pend)) == 0) {
+        if constexpr ((F & F_COUNT) != 0) {
+          ++cnt.islot;
+          kinds = K_WIDE;
+        }
+        if (t.node >= 0) wide_inner<F, PK>(S, t, stk, stride, cnt);
+      } else {
+        if constexpr ((F & F_COUNT) != 0) {
+          ++cnt.lslot;
+          kinds = K_LEAF;
+        }
+        if (rt_wlane_holding(t.pend)) wide_leaf<F, PK>(S, t, t_min, stk, stride, cnt, g, side);
+      }
+      if constexpr ((F & F_COUNT) != 0) {  // (step profile: wide steps, leaf steps)
+        const unsigned long long t1 = stamp();
+        if (cnt.prof && __lane_id() == (unsigned)(__ffsll((long long)__ballot(true)) - 1)) {
+          atomicAdd(&cnt.prof[kinds], t1 - t0);
+          atomicAdd(&cnt.prof[32 + kinds], 1ull);
+        }
+      }
+    }
+    walking = rt_wlane_walking(t.node, t.pend);
   } else {
     for (;;) {
       if (__popcll(__ballot(walking)) <= stop) break;
