@@ -47,11 +47,11 @@ __host__ __device__ __forceinline__ uint32_t udiv(uint32_t n, UDiv d) {
 }
 
 // The launch's constants: everything a launch passes to its kernels. The small kernels (combine_chunks,
-// tail_combine, frame_resolve) and tier A take it by value. The tier-B render kernels get a device copy
-// (RenderArgs::lc, written by launch_setup ahead of the launch) and stage it in LDS once per workgroup:
-// the persistent loops read the camera, the table pointers, the work geometry and the claim parameters
-// from there where they use them, instead of holding them in scalar registers (and their spill lanes)
-// across the walk. DESIGN.md §3.1.
+// tail_combine) and tier A take it by value, and so do a progressive frame's frame_* helpers, which read the frame
+// geometry, acc, chunk, spp and out_rgb / out_lin. The tier-B render kernels get a device copy (RenderArgs::lc,
+// written by launch_setup ahead of the launch) and stage it in LDS once per workgroup: the persistent loops read
+// the camera, the table pointers, the work geometry and the claim parameters from there where they use them,
+// instead of holding them in scalar registers (and their spill lanes) across the walk. DESIGN.md §3.1.
 struct LaunchConst {
   Scene S;
   rt_camera cam;
@@ -937,6 +937,17 @@ __global__ void assemble(const T* slabs, T* image, int W, int H, int tile, int t
 }
 
 // ---------------------------------------------------------------- progressive frames (rt_frame_*)
+// The helper kernels of a progressive frame, one set for both traversal orders (SLAB). An unsharded frame
+// (SLAB = false) keeps its previews, its error map and its copy of K_p in image order and runs one thread
+// per image pixel. A shard frame (SLAB = true, rt.h) is a frame over the slab of (tile, shard_rank,
+// shard_count): it keeps all of them in slab order and runs one thread per slab pixel, so its reads and
+// writes are contiguous in the slab. Sums, moments and kp are in slab order in both. A carries the frame's
+// geometry (fill_frame_geometry with the frame's own shard; an unsharded frame is shard 0 of 1), its sums
+// (A.acc) and what a stopped pixel's N_p needs (A.chunk, A.spp). `kp` is an adaptive frame's K_p per slab
+// pixel (0 = active); null: no stop call yet, every pixel is active. frame_resolve and frame_error read it
+// under ADAPT only, the instantiation a frame takes once it has a kp: as a run-time test in the one kernel it
+// cost a C2 frame's rt_frame_error 1.4 us of 119.
+
 // Image pixel -> its slot in an unsharded slab (assemble's map at shards = 1).
 __device__ __forceinline__ long long frame_slot(long long i, int W, int tile, int tiles_x) {
   const int row = (int)(i / W), px = (int)(i % W);
@@ -946,251 +957,39 @@ __device__ __forceinline__ long long frame_slot(long long i, int W, int tile, in
   return lt * tile * tile + (by * bpr + bx) * 64 + (row & 7) * 8 + (px & 7);
 }
 
-// A frame's preview: the running sums (A.acc, slab order) over `samples` samples, averaged and stored as
-// combine_chunks' last batch stores them (divide, store_pixel), in image order: A.out_rgb / A.out_lin are
-// the frame's H*W*3 image buffers (out_lin may be null). A.out_rgb still holds the previous preview:
-// counts[0] += pixels whose sum has a NaN channel, counts[1] += bytes that change. One pass; the counts
-// are reduced over each wave with ballots, over the block's 4 waves through LDS, and leave the block as
-// one atomic per counter.
-// ADAPT (an adaptive frame, rt.h): a stopped pixel (kp[slab pixel] = K_p != 0) is averaged over its own
-// N_p = min(spp, K_p * CH) samples (A.spp, A.chunk); an active pixel over `samples`.
-template <bool ADAPT>
-__device__ __forceinline__ void resolve_body(const LaunchConst& A, int samples, unsigned long long* counts,
-                                             const int* kp) {
-  __shared__ unsigned wave_nan[4], wave_chg[4];
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  bool nan = false, c0 = false, c1 = false, c2 = false;
-  if (i < (long long)A.W * A.H) {
-    const long long slot = frame_slot(i, A.W, A.tile, A.tiles_x);
-    const V3 sum = vload(A.acc + slot * 3);
-    nan = sum.x != sum.x || sum.y != sum.y || sum.z != sum.z;
-    if constexpr (ADAPT) {
-      const long long n = (long long)kp[slot] * A.chunk;
-      if (n) samples = n < A.spp ? (int)n : A.spp;
-    }
-    const V3 avg = divide(sum, (double)samples);
-    const uint8_t p0 = A.out_rgb[i * 3 + 0], p1 = A.out_rgb[i * 3 + 1], p2 = A.out_rgb[i * 3 + 2];
-    store_pixel(A, i, avg);
-    c0 = scale_color(avg.x) != p0;
-    c1 = scale_color(avg.y) != p1;
-    c2 = scale_color(avg.z) != p2;
+// Thread t's pixel. False: it has none (past the image; in slab order also a padding slot, outside the
+// image or of a tile past the image's last when there are more shards than tiles: never read, never
+// written, never counted). Else `slot` is where the pixel's sums, moments and kp live and `img` is
+// row * W + px. A kernel's own outputs (preview, se, K_p copy) and the previous preview are at index t in
+// both orders.
+template <bool SLAB>
+__device__ __forceinline__ bool frame_pixel(const LaunchConst& A, long long t, long long& slot, long long& img) {
+  if constexpr (SLAB) {
+    int px, row;
+    if (t >= A.slab || !work_pixel(A, (uint32_t)t, px, row)) return false;
+    slot = t;
+    img = (long long)row * A.W + px;
+  } else {
+    if (t >= (long long)A.W * A.H) return false;
+    slot = frame_slot(t, A.W, A.tile, A.tiles_x);
+    img = t;
   }
-  const unsigned n_nan = (unsigned)__popcll(__ballot(nan));
-  const unsigned n_chg = (unsigned)(__popcll(__ballot(c0)) + __popcll(__ballot(c1)) + __popcll(__ballot(c2)));
-  if ((threadIdx.x & 63) == 0) {
-    wave_nan[threadIdx.x >> 6] = n_nan;
-    wave_chg[threadIdx.x >> 6] = n_chg;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned bn = wave_nan[0] + wave_nan[1] + wave_nan[2] + wave_nan[3];
-    const unsigned bc = wave_chg[0] + wave_chg[1] + wave_chg[2] + wave_chg[3];
-    if (bn) atomicAdd(&counts[0], (unsigned long long)bn);
-    if (bc) atomicAdd(&counts[1], (unsigned long long)bc);
-  }
-}
-__global__ void __launch_bounds__(256) frame_resolve(LaunchConst A, int samples, unsigned long long* counts) {
-  resolve_body<false>(A, samples, counts, nullptr);
-}
-__global__ void __launch_bounds__(256) frame_resolve_adapt(LaunchConst A, int samples, unsigned long long* counts,
-                                                           const int* kp) {
-  resolve_body<true>(A, samples, counts, kp);
+  return true;
 }
 
-// Saved sums (image order) back into a frame's slab-order running sums: assemble<double>'s inverse at
-// shards = 1 (rt_frame_restore; the slab's padding pixels are never read).
-__global__ void __launch_bounds__(256) frame_scatter(const double* image, double* sums, int W, int H, int tile,
-                                                     int tiles_x) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)W * H) return;
-  const long long dst = frame_slot(i, W, tile, tiles_x);
-  sums[dst * 3 + 0] = image[i * 3 + 0];
-  sums[dst * 3 + 1] = image[i * 3 + 1];
-  sums[dst * 3 + 2] = image[i * 3 + 2];
+// A stopped pixel of an adaptive frame (kp[slot] = K_p != 0) is averaged and estimated at its own K_p chunks
+// and N_p = min(spp, K_p * CH) samples; an active pixel keeps the frame's `chunks` and `samples`.
+__device__ __forceinline__ void pixel_counts(const LaunchConst& A, const int* kp, long long slot, int& chunks,
+                                             int& samples) {
+  const int k = kp ? kp[slot] : 0;
+  if (!k) return;
+  const long long n = (long long)k * A.chunk;
+  chunks = k;
+  samples = n < A.spp ? (int)n : A.spp;
 }
-
-// A tracked frame's error map and summary (rt.h): one thread per image pixel reads its sums and moments
-// (slab order, through frame_slot), computes se[3] (rt::pixel_error, the host's text) and stores it in image
-// order when `out_se` is given. acc[0] += non-finite pixels, acc[1] += finite unconverged pixels (ballots
-// per wave, LDS over the block's 4 waves, one atomic per block and counter, as frame_resolve's counts);
-// acc[2] = max se over the finite pixels' channels, as the value's bit pattern (non-negative finite doubles
-// order as unsigned integers: a lane-shuffle max per wave, LDS, one atomicMax per block); and the block's
-// sum of those se in a fixed order (a pixel's channels in order, a wave's lanes by halving shuffles, the
-// waves in wave order) to block_sums[blockIdx.x]: frame_error_sum adds them, so the total has no
-// floating-point atomic in it and repeats.
-// ADAPT (an adaptive frame, rt.h): a stopped pixel (kp[slab pixel] = K_p != 0) is estimated at its own
-// (K_p, N_p = min(spp, K_p * chunk)); with K_p < 2 it is non-finite, its se channels NaN.
-template <bool ADAPT>
-__device__ __forceinline__ void error_body(const double* sums, const double* moments, double* out_se, int W, int H,
-                                           int tile, int tiles_x, int chunks, int samples, double abs_tol,
-                                           double rel_tol, unsigned long long* acc, double* block_sums,
-                                           const int* kp, int chunk, int spp) {
-  __shared__ unsigned wave_bad[4], wave_open[4];
-  __shared__ unsigned long long wave_max[4];
-  __shared__ double wave_sum[4];
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  bool bad = false, open = false;
-  double sum = 0.0;
-  unsigned long long top = 0ull;
-  if (i < (long long)W * H) {
-    const long long slot = frame_slot(i, W, tile, tiles_x) * 3;
-    const double s[3] = {sums[slot], sums[slot + 1], sums[slot + 2]};
-    const double q[3] = {moments[slot], moments[slot + 1], moments[slot + 2]};
-    double se[3];
-    if constexpr (ADAPT) {
-      const int k = kp[slot / 3];
-      if (k) {
-        const long long n = (long long)k * chunk;
-        chunks = k;
-        samples = n < spp ? (int)n : spp;
-      }
-    }
-    int cls = rt::kPixelNonFinite;
-    if (!ADAPT || chunks >= 2) {
-      cls = rt::pixel_error(s, q, chunks, samples, abs_tol, rel_tol, se);
-    } else {
-      se[0] = se[1] = se[2] = __longlong_as_double(0x7ff8000000000000ll);
-    }
-    if (out_se) {
-      out_se[i * 3 + 0] = se[0];
-      out_se[i * 3 + 1] = se[1];
-      out_se[i * 3 + 2] = se[2];
-    }
-    bad = cls == rt::kPixelNonFinite;
-    open = cls == rt::kPixelUnconverged;
-    if (!bad) {
-      sum = (se[0] + se[1]) + se[2];
-      const double m = fmax(fmax(se[0], se[1]), se[2]);
-      top = (unsigned long long)__double_as_longlong(m);
-    }
-  }
-  const unsigned n_bad = (unsigned)__popcll(__ballot(bad)), n_open = (unsigned)__popcll(__ballot(open));
-  for (int off = 32; off > 0; off >>= 1) {
-    sum = sum + __shfl_down(sum, off, 64);
-    const unsigned long long other = __shfl_down(top, off, 64);
-    top = other > top ? other : top;
-  }
-  if ((threadIdx.x & 63) == 0) {
-    const int w = threadIdx.x >> 6;
-    wave_bad[w] = n_bad;
-    wave_open[w] = n_open;
-    wave_max[w] = top;
-    wave_sum[w] = sum;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned nb = wave_bad[0] + wave_bad[1] + wave_bad[2] + wave_bad[3];
-    const unsigned no = wave_open[0] + wave_open[1] + wave_open[2] + wave_open[3];
-    unsigned long long m = wave_max[0];
-    for (int w = 1; w < 4; ++w) m = wave_max[w] > m ? wave_max[w] : m;
-    if (nb) atomicAdd(&acc[0], (unsigned long long)nb);
-    if (no) atomicAdd(&acc[1], (unsigned long long)no);
-    if (m) atomicMax(&acc[2], m);
-    block_sums[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-  }
-}
-__global__ void __launch_bounds__(256) frame_error(const double* sums, const double* moments, double* out_se, int W,
-                                                   int H, int tile, int tiles_x, int chunks, int samples,
-                                                   double abs_tol, double rel_tol, unsigned long long* acc,
-                                                   double* block_sums) {
-  error_body<false>(sums, moments, out_se, W, H, tile, tiles_x, chunks, samples, abs_tol, rel_tol, acc, block_sums,
-                    nullptr, 0, 0);
-}
-__global__ void __launch_bounds__(256) frame_error_adapt(const double* sums, const double* moments, double* out_se,
-                                                         int W, int H, int tile, int tiles_x, int chunks, int samples,
-                                                         double abs_tol, double rel_tol, unsigned long long* acc,
-                                                         double* block_sums, const int* kp, int chunk, int spp) {
-  error_body<true>(sums, moments, out_se, W, H, tile, tiles_x, chunks, samples, abs_tol, rel_tol, acc, block_sums, kp,
-                   chunk, spp);
-}
-
-// Adaptive frames (rt.h): stops active pixels, by the rule (RULE: rt::adapt_pixel, the host's text, at the
-// frame's K chunks and N samples) or by the caller's image-order byte mask. One thread per slab pixel, so
-// that a wave is one word of the skip bitmask (64 consecutive slab pixels, one 8x8 block; work_pixel is
-// frame_slot's inverse): a newly stopped pixel gets kp = K, and the wave's lane 0 writes the word from one
-// ballot of "stopped before or now" (padding pixels outside the image: never set, never counted).
-// counts[0] += pixels stopped by this call, counts[1] += those of them whose sum has a NaN channel, reduced
-// as frame_resolve reduces its counts.
-template <bool RULE>
-__device__ __forceinline__ void adapt_body(const LaunchConst& A, const double* moments, int* kp,
-                                           unsigned long long* skip, const uint8_t* mask, int K, int N,
-                                           rt_adapt_rule rule, unsigned long long* counts) {
-  __shared__ unsigned wave_now[4], wave_nan[4];
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  bool stopped = false, now = false, now_nan = false;
-  int px, row;
-  if (idx < A.slab && work_pixel(A, (uint32_t)idx, px, row)) {
-    stopped = kp[idx] != 0;
-    if (!stopped) {
-      const double s[3] = {A.acc[idx * 3], A.acc[idx * 3 + 1], A.acc[idx * 3 + 2]};
-      if constexpr (RULE) {
-        double q[3] = {0.0, 0.0, 0.0};
-        if (moments) q[0] = moments[idx * 3], q[1] = moments[idx * 3 + 1], q[2] = moments[idx * 3 + 2];
-        now = rt::adapt_pixel(s, q, K, N, rule.flags, rule.abs_tol, rule.rel_tol, rule.min_chunks) != rt::kAdaptKeep;
-      } else {
-        now = mask[(long long)row * A.W + px] != 0;
-      }
-      if (now) {
-        kp[idx] = K;
-        now_nan = s[0] != s[0] || s[1] != s[1] || s[2] != s[2];
-      }
-    }
-  }
-  const unsigned long long word = __ballot(stopped || now);
-  const unsigned n_now = (unsigned)__popcll(__ballot(now)), n_nan = (unsigned)__popcll(__ballot(now_nan));
-  if ((threadIdx.x & 63) == 0) {
-    if (idx < A.slab) skip[idx >> 6] = word;  // (the slab is whole 8x8 blocks: a wave is inside it or past it)
-    wave_now[threadIdx.x >> 6] = n_now;
-    wave_nan[threadIdx.x >> 6] = n_nan;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned bn = wave_now[0] + wave_now[1] + wave_now[2] + wave_now[3];
-    const unsigned bq = wave_nan[0] + wave_nan[1] + wave_nan[2] + wave_nan[3];
-    if (bn) atomicAdd(&counts[0], (unsigned long long)bn);
-    if (bq) atomicAdd(&counts[1], (unsigned long long)bq);
-  }
-}
-__global__ void __launch_bounds__(256) frame_adapt(LaunchConst A, const double* moments, int* kp,
-                                                   unsigned long long* skip, int K, int N, rt_adapt_rule rule,
-                                                   unsigned long long* counts) {
-  adapt_body<true>(A, moments, kp, skip, nullptr, K, N, rule, counts);
-}
-__global__ void __launch_bounds__(256) frame_stop_mask(LaunchConst A, int* kp, unsigned long long* skip,
-                                                       const uint8_t* mask, int K, unsigned long long* counts) {
-  adapt_body<false>(A, nullptr, kp, skip, mask, K, 0, rt_adapt_rule{}, counts);
-}
-
-// K_p in image order (rt_frame_chunk_counts): a stopped pixel's kp, else the frame's K.
-__global__ void __launch_bounds__(256) frame_chunk_counts(const int* kp, int* out, int W, int H, int tile,
-                                                          int tiles_x, int K) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)W * H) return;
-  const int k = kp[frame_slot(i, W, tile, tiles_x)];
-  out[i] = k ? k : K;
-}
-
-// frame_error's block sums added in a fixed order by one block: thread t adds blocks t, t + 256, ... in
-// block order, then the threads' sums fold as a block's do (lanes by halving shuffles, waves in wave order).
-__global__ void __launch_bounds__(256) frame_error_sum(const double* block_sums, int blocks, double* out) {
-  __shared__ double wave_sum[4];
-  double sum = 0.0;
-  for (int b = threadIdx.x; b < blocks; b += 256) sum = sum + block_sums[b];
-  for (int off = 32; off > 0; off >>= 1) sum = sum + __shfl_down(sum, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-}
-
-// ---------------------------------------------------------------- shard frames (rt_frame_*_shard)
-// A shard frame (rt.h) is a progressive frame over the slab of (tile, shard_rank, shard_count): its sums,
-// moments, K_p, previews and error map all stay in slab order, and these kernels run one thread per slab
-// pixel through work_pixel, as adapt_body does (A's frame geometry: fill_frame_geometry with the shard).
-// A slab pixel outside the image, or of a tile past the image's last (more shards than tiles), is padding:
-// never read, never written, never counted. Reads and writes are contiguous in the slab.
 
 // Two per-wave counts (a wave's ballots, already popcounted) summed over the block's 4 waves through LDS;
-// they leave the block as at most one atomic per counter (frame_resolve's reduction).
+// they leave the block as at most one atomic per counter.
 __device__ __forceinline__ void block_add2(unsigned a, unsigned b, unsigned long long* counts) {
   __shared__ unsigned wave_a[4], wave_b[4];
   if ((threadIdx.x & 63) == 0) {
@@ -1206,25 +1005,28 @@ __device__ __forceinline__ void block_add2(unsigned a, unsigned b, unsigned long
   }
 }
 
-// frame_resolve in slab order: A.out_rgb / A.out_lin are the shard frame's own slab*3 preview buffers
-// (A.out_rgb holds the previous preview), the per-pixel arithmetic is resolve_body's, so the assembled
-// slabs of all shards are the unsharded preview bit for bit and the counts add up to its counts.
-template <bool ADAPT>
-__device__ __forceinline__ void resolve_slab_body(const LaunchConst& A, int samples, unsigned long long* counts,
-                                                  const int* kp) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+// A frame's preview: the running sums (A.acc) over `samples` samples (a stopped pixel: over its own N_p),
+// averaged and stored as combine_chunks' last batch stores them (divide, store_pixel) in the frame's order:
+// A.out_rgb / A.out_lin are its H*W*3 image buffers, or a shard frame's slab*3 buffers (out_lin may be
+// null). A.out_rgb still holds the previous preview: counts[0] += pixels whose sum has a NaN channel,
+// counts[1] += bytes that change (block_add2). The per-pixel arithmetic does not depend on the order, so the
+// assembled slabs of all shards are the unsharded preview bit for bit and their counts add up to its counts.
+template <bool SLAB, bool ADAPT>
+__global__ void __launch_bounds__(256) frame_resolve(LaunchConst A, int samples, unsigned long long* counts,
+                                                     const int* kp) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   bool nan = false, c0 = false, c1 = false, c2 = false;
-  int px, row;
-  if (idx < A.slab && work_pixel(A, (uint32_t)idx, px, row)) {
-    const V3 sum = vload(A.acc + idx * 3);
+  long long slot, img;
+  if (frame_pixel<SLAB>(A, t, slot, img)) {
+    const V3 sum = vload(A.acc + slot * 3);
     nan = sum.x != sum.x || sum.y != sum.y || sum.z != sum.z;
     if constexpr (ADAPT) {
-      const long long n = (long long)kp[idx] * A.chunk;
-      if (n) samples = n < A.spp ? (int)n : A.spp;
+      int chunks = 0;
+      pixel_counts(A, kp, slot, chunks, samples);
     }
     const V3 avg = divide(sum, (double)samples);
-    const uint8_t p0 = A.out_rgb[idx * 3 + 0], p1 = A.out_rgb[idx * 3 + 1], p2 = A.out_rgb[idx * 3 + 2];
-    store_pixel(A, idx, avg);
+    const uint8_t p0 = A.out_rgb[t * 3 + 0], p1 = A.out_rgb[t * 3 + 1], p2 = A.out_rgb[t * 3 + 2];
+    store_pixel(A, t, avg);
     c0 = scale_color(avg.x) != p0;
     c1 = scale_color(avg.y) != p1;
     c2 = scale_color(avg.z) != p2;
@@ -1233,42 +1035,46 @@ __device__ __forceinline__ void resolve_slab_body(const LaunchConst& A, int samp
   const unsigned n_chg = (unsigned)(__popcll(__ballot(c0)) + __popcll(__ballot(c1)) + __popcll(__ballot(c2)));
   block_add2(n_nan, n_chg, counts);
 }
-__global__ void __launch_bounds__(256) frame_resolve_slab(LaunchConst A, int samples, unsigned long long* counts) {
-  resolve_slab_body<false>(A, samples, counts, nullptr);
-}
-__global__ void __launch_bounds__(256) frame_resolve_slab_adapt(LaunchConst A, int samples,
-                                                                unsigned long long* counts, const int* kp) {
-  resolve_slab_body<true>(A, samples, counts, kp);
+
+// Saved sums or moments (image order, the whole image) into a frame's slab-order buffer: every pixel of the
+// frame's slab fetches its image pixel (rt_frame_restore*). Unsharded, this is assemble<double>'s inverse at
+// shards = 1; a shard frame takes the pixels it owns and leaves the other shards' alone.
+template <bool SLAB>
+__global__ void __launch_bounds__(256) frame_scatter(LaunchConst A, const double* image, double* sums) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  long long slot, img;
+  if (!frame_pixel<SLAB>(A, t, slot, img)) return;
+  sums[slot * 3 + 0] = image[img * 3 + 0];
+  sums[slot * 3 + 1] = image[img * 3 + 1];
+  sums[slot * 3 + 2] = image[img * 3 + 2];
 }
 
-// frame_error in slab order: sums A.acc and `moments` by slab pixel, se stored by slab pixel in `out_se`
-// (the caller's device buffer, may be null; padding slots are left alone). acc[0..2] and block_sums as
-// error_body fills them: exact counts and maximum, and one partial sum per block in a fixed order (a
-// pixel's channels, a wave's lanes by halving shuffles, the waves in wave order) for frame_error_sum, so
-// the shard's mean has no floating-point atomic in it and repeats.
-template <bool ADAPT>
-__device__ __forceinline__ void error_slab_body(const LaunchConst& A, const double* moments, double* out_se,
-                                                int chunks, int samples, double abs_tol, double rel_tol,
-                                                unsigned long long* acc, double* block_sums, const int* kp) {
+// A tracked frame's error map and summary (rt.h): a thread reads its pixel's sums (A.acc) and `moments`,
+// computes se[3] (rt::pixel_error, the host's text) at the frame's `chunks` >= 2 and `samples`, or at a
+// stopped pixel's own (K_p, N_p): with K_p < 2 that pixel is non-finite, its se channels NaN. `out_se`, when
+// given, gets se in the frame's order (device memory; a shard frame's padding slots are left alone).
+// acc[0] += non-finite pixels, acc[1] += finite unconverged pixels (block_add2); acc[2] = max se over the
+// finite pixels' channels, as the value's bit pattern (non-negative finite doubles order as unsigned
+// integers: a lane-shuffle max per wave, LDS, one atomicMax per block); and the block's sum of those se in a
+// fixed order (a pixel's channels in order, a wave's lanes by halving shuffles, the waves in wave order) to
+// block_sums[blockIdx.x]: frame_error_sum adds them, so the total has no floating-point atomic in it and
+// repeats.
+template <bool SLAB, bool ADAPT>
+__global__ void __launch_bounds__(256) frame_error(LaunchConst A, const double* moments, double* out_se, int chunks,
+                                                   int samples, double abs_tol, double rel_tol,
+                                                   unsigned long long* acc, double* block_sums, const int* kp) {
   __shared__ unsigned long long wave_max[4];
   __shared__ double wave_sum[4];
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   bool bad = false, open = false;
   double sum = 0.0;
   unsigned long long top = 0ull;
-  int px, row;
-  if (idx < A.slab && work_pixel(A, (uint32_t)idx, px, row)) {
-    const double s[3] = {A.acc[idx * 3], A.acc[idx * 3 + 1], A.acc[idx * 3 + 2]};
-    const double q[3] = {moments[idx * 3], moments[idx * 3 + 1], moments[idx * 3 + 2]};
+  long long slot, img;
+  if (frame_pixel<SLAB>(A, t, slot, img)) {
+    const double s[3] = {A.acc[slot * 3], A.acc[slot * 3 + 1], A.acc[slot * 3 + 2]};
+    const double q[3] = {moments[slot * 3], moments[slot * 3 + 1], moments[slot * 3 + 2]};
     double se[3];
-    if constexpr (ADAPT) {
-      const int k = kp[idx];
-      if (k) {
-        const long long n = (long long)k * A.chunk;
-        chunks = k;
-        samples = n < A.spp ? (int)n : A.spp;
-      }
-    }
+    if constexpr (ADAPT) pixel_counts(A, kp, slot, chunks, samples);
     int cls = rt::kPixelNonFinite;
     if (!ADAPT || chunks >= 2) {
       cls = rt::pixel_error(s, q, chunks, samples, abs_tol, rel_tol, se);
@@ -1276,9 +1082,9 @@ __device__ __forceinline__ void error_slab_body(const LaunchConst& A, const doub
       se[0] = se[1] = se[2] = __longlong_as_double(0x7ff8000000000000ll);
     }
     if (out_se) {
-      out_se[idx * 3 + 0] = se[0];
-      out_se[idx * 3 + 1] = se[1];
-      out_se[idx * 3 + 2] = se[2];
+      out_se[t * 3 + 0] = se[0];
+      out_se[t * 3 + 1] = se[1];
+      out_se[t * 3 + 2] = se[2];
     }
     bad = cls == rt::kPixelNonFinite;
     open = cls == rt::kPixelUnconverged;
@@ -1306,36 +1112,75 @@ __device__ __forceinline__ void error_slab_body(const LaunchConst& A, const doub
     block_sums[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
   }
 }
-__global__ void __launch_bounds__(256) frame_error_slab(LaunchConst A, const double* moments, double* out_se,
-                                                        int chunks, int samples, double abs_tol, double rel_tol,
-                                                        unsigned long long* acc, double* block_sums) {
-  error_slab_body<false>(A, moments, out_se, chunks, samples, abs_tol, rel_tol, acc, block_sums, nullptr);
-}
-__global__ void __launch_bounds__(256) frame_error_slab_adapt(LaunchConst A, const double* moments, double* out_se,
-                                                              int chunks, int samples, double abs_tol,
-                                                              double rel_tol, unsigned long long* acc,
-                                                              double* block_sums, const int* kp) {
-  error_slab_body<true>(A, moments, out_se, chunks, samples, abs_tol, rel_tol, acc, block_sums, kp);
+
+// frame_error's block sums added in a fixed order by one block: thread t adds blocks t, t + 256, ... in
+// block order, then the threads' sums fold as a block's do (lanes by halving shuffles, waves in wave order).
+__global__ void __launch_bounds__(256) frame_error_sum(const double* block_sums, int blocks, double* out) {
+  __shared__ double wave_sum[4];
+  double sum = 0.0;
+  for (int b = threadIdx.x; b < blocks; b += 256) sum = sum + block_sums[b];
+  for (int off = 32; off > 0; off >>= 1) sum = sum + __shfl_down(sum, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
 }
 
-// Saved sums or moments (image order, the whole image) into a shard frame's slab: each slab pixel the shard
-// owns fetches its image pixel (rt_frame_restore_shard); the other shards' pixels are not touched.
-__global__ void __launch_bounds__(256) frame_scatter_slab(LaunchConst A, const double* image, double* sums) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  int px, row;
-  if (idx >= A.slab || !work_pixel(A, (uint32_t)idx, px, row)) return;
-  const long long i = (long long)row * A.W + px;
-  sums[idx * 3 + 0] = image[i * 3 + 0];
-  sums[idx * 3 + 1] = image[i * 3 + 1];
-  sums[idx * 3 + 2] = image[i * 3 + 2];
+// K_p in the frame's order (rt_frame_chunk_counts, rt_frame_shard_state): a stopped pixel's kp, else the
+// frame's K.
+template <bool SLAB>
+__global__ void __launch_bounds__(256) frame_chunk_counts(LaunchConst A, const int* kp, int* out, int K) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  long long slot, img;
+  if (!frame_pixel<SLAB>(A, t, slot, img)) return;
+  const int k = kp ? kp[slot] : 0;
+  out[t] = k ? k : K;
 }
 
-// K_p in slab order (rt_frame_shard_state): a stopped pixel's kp, else the frame's K; kp null: no stop call yet.
-__global__ void __launch_bounds__(256) frame_chunk_counts_slab(const int* kp, int* out, long long slab, int K) {
+// Adaptive frames (rt.h): stops active pixels, by the rule (RULE: rt::adapt_pixel, the host's text, at the
+// frame's K chunks and N samples) or by the caller's image-order byte mask. One thread per slab pixel in
+// both kinds of frame, so that a wave is one word of the skip bitmask (64 consecutive slab pixels, one 8x8
+// block; work_pixel is frame_slot's inverse): a newly stopped pixel gets kp = K, and the wave's lane 0
+// writes the word from one ballot of "stopped before or now" (padding pixels outside the image: never set,
+// never counted). counts[0] += pixels stopped by this call, counts[1] += those of them whose sum has a NaN
+// channel (block_add2).
+template <bool RULE>
+__device__ __forceinline__ void adapt_body(const LaunchConst& A, const double* moments, int* kp,
+                                           unsigned long long* skip, const uint8_t* mask, int K, int N,
+                                           rt_adapt_rule rule, unsigned long long* counts) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= slab) return;
-  const int k = kp ? kp[idx] : 0;
-  out[idx] = k ? k : K;
+  bool stopped = false, now = false, now_nan = false;
+  long long slot, img;
+  if (frame_pixel<true>(A, idx, slot, img)) {
+    stopped = kp[idx] != 0;
+    if (!stopped) {
+      const double s[3] = {A.acc[idx * 3], A.acc[idx * 3 + 1], A.acc[idx * 3 + 2]};
+      if constexpr (RULE) {
+        double q[3] = {0.0, 0.0, 0.0};
+        if (moments) q[0] = moments[idx * 3], q[1] = moments[idx * 3 + 1], q[2] = moments[idx * 3 + 2];
+        now = rt::adapt_pixel(s, q, K, N, rule.flags, rule.abs_tol, rule.rel_tol, rule.min_chunks) != rt::kAdaptKeep;
+      } else {
+        now = mask[img] != 0;
+      }
+      if (now) {
+        kp[idx] = K;
+        now_nan = s[0] != s[0] || s[1] != s[1] || s[2] != s[2];
+      }
+    }
+  }
+  const unsigned long long word = __ballot(stopped || now);
+  const unsigned n_now = (unsigned)__popcll(__ballot(now)), n_nan = (unsigned)__popcll(__ballot(now_nan));
+  // (the slab is whole 8x8 blocks: a wave is inside it or past it)
+  if ((threadIdx.x & 63) == 0 && idx < A.slab) skip[idx >> 6] = word;
+  block_add2(n_now, n_nan, counts);
+}
+__global__ void __launch_bounds__(256) frame_adapt(LaunchConst A, const double* moments, int* kp,
+                                                   unsigned long long* skip, int K, int N, rt_adapt_rule rule,
+                                                   unsigned long long* counts) {
+  adapt_body<true>(A, moments, kp, skip, nullptr, K, N, rule, counts);
+}
+__global__ void __launch_bounds__(256) frame_stop_mask(LaunchConst A, int* kp, unsigned long long* skip,
+                                                       const uint8_t* mask, int K, unsigned long long* counts) {
+  adapt_body<false>(A, nullptr, kp, skip, mask, K, 0, rt_adapt_rule{}, counts);
 }
 
 // ---------------------------------------------------------------- debug: closest hits

@@ -102,9 +102,11 @@ struct rt_ctx {
   uint32_t upload_flags = 0;
 };
 
-// A progressive frame (rt.h): the running per-pixel sums of the chunks rendered so far, in the slab
-// order of an unsharded launch, and the image-order buffers of its previews. All its work is queued on
-// the ctx's stream.
+// A progressive frame (rt.h): the running per-pixel sums of the chunks rendered so far, in the slab order
+// of its shard's launch (`p`'s shard fields; an unsharded frame is shard 0 of 1), and the buffers of its
+// previews in the frame's own order: image order, or a shard frame's slab order. One set of helper kernels
+// (rt_kernels.h frame_*<SLAB>, launched through FRAME_KERNEL* with frame_const's constants) and one *_run
+// function per call serve both kinds. All its work is queued on the ctx's stream.
 struct rt_frame {
   rt_ctx* ctx = nullptr;
   bool valid = true;  // false once the ctx's scene was replaced
@@ -118,9 +120,9 @@ struct rt_frame {
   bool shard = false;
   long long owned = 0;
   double* d_sum = nullptr;   // [slab pixel][3]
-  uint8_t* d_rgb = nullptr;  // the last preview's bytes (zero before the first), H*W*3
-  double* d_lin = nullptr;   // the last linear preview, H*W*3
-  double* d_stage = nullptr; // save's and restore's image-order copy of the sums, H*W*3, on first use
+  uint8_t* d_rgb = nullptr;  // the last preview's bytes (zero before the first), H*W*3 (shard frame: slab*3)
+  double* d_lin = nullptr;   // the last linear preview, H*W*3 (shard frame: slab*3)
+  double* d_stage = nullptr; // unsharded: save's and restore's image-order copy of the sums, H*W*3, on first use
   unsigned long long* d_counts = nullptr;  // frame_resolve's {nan_pixels, bytes_changed}
   // RT_FRAME_MOMENTS: the second moments Q of the chunk sums, [slab pixel][3] like d_sum (else null);
   // frame_error's image-order map, H*W*3, and its {non-finite, unconverged, max bits, sum} followed by one
@@ -1349,12 +1351,131 @@ void frame_write_header(const rt_frame* f, uint8_t* buf) {
   rt::blob_write_header(b, buf);
 }
 
-// The frame's geometry and sums in launch constants, for the slab-order kernels of a shard frame.
-void shard_const(const rt_frame* f, LaunchConst& A) {
+// The frame's geometry and sums in launch constants, for its frame_* helper kernels (rt_kernels.h): the
+// frame's own shard, an unsharded frame being shard 0 of 1.
+void frame_const(const rt_frame* f, LaunchConst& A) {
   long long per_shard;
   fill_frame_geometry(A, &f->p, f->p.shard_rank, f->p.shard_count, per_shard);
   A.chunk = f->chunk;  // (rt.h's, whatever RTAMD_CHUNK says: frame_new refuses the override)
   A.acc = f->d_sum;
+}
+
+// The samples in the frame's sums so far (the last chunk may be short).
+int frame_samples(const rt_frame* f) {
+  return (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
+}
+
+// Threads of a frame_* helper launch: one per pixel of the frame's order (image, or a shard frame's slab).
+long long frame_threads(const rt_frame* f) { return f->shard ? f->slab : f->npx; }
+dim3 frame_grid(const rt_frame* f) { return dim3((unsigned)((frame_threads(f) + 255) / 256)); }
+
+// The frame's order selects the helper kernel's instantiation: FRAME_KERNEL(f, frame_scatter, args...); for
+// frame_resolve and frame_error so does whether a stop call has given it a kp (FRAME_KERNEL_ADAPT).
+#define FRAME_LAUNCH(f, kernel, ...) \
+  hipLaunchKernelGGL((kernel), frame_grid(f), dim3(256), 0, (f)->ctx->stream, __VA_ARGS__)
+#define FRAME_KERNEL(f, kernel, ...)                 \
+  do {                                               \
+    if ((f)->shard)                                  \
+      FRAME_LAUNCH(f, kernel<true>, __VA_ARGS__);    \
+    else                                             \
+      FRAME_LAUNCH(f, kernel<false>, __VA_ARGS__);   \
+  } while (0)
+#define FRAME_KERNEL_ADAPT(f, kernel, ...)                  \
+  do {                                                      \
+    if ((f)->shard && (f)->d_kp)                            \
+      FRAME_LAUNCH(f, (kernel<true, true>), __VA_ARGS__);   \
+    else if ((f)->shard)                                    \
+      FRAME_LAUNCH(f, (kernel<true, false>), __VA_ARGS__);  \
+    else if ((f)->d_kp)                                     \
+      FRAME_LAUNCH(f, (kernel<false, true>), __VA_ARGS__);  \
+    else                                                    \
+      FRAME_LAUNCH(f, (kernel<false, false>), __VA_ARGS__); \
+  } while (0)
+
+// A new preview in the frame's own buffers (d_rgb, d_lin) and its counts in f->last (the ctx's device is
+// selected, a chunk has been rendered since the last resolve).
+int frame_resolve_run(rt_frame* f) {
+  rt_ctx* c = f->ctx;
+  LaunchConst A{};
+  frame_const(f, A);
+  A.out_rgb = f->d_rgb;
+  A.out_lin = f->d_lin;
+  const int samples = frame_samples(f);
+  HIPCHK(hipMemsetAsync(f->d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+  // (an adapted frame: each stopped pixel over its own N_p = min(spp, K_p * CH))
+  FRAME_KERNEL_ADAPT(f, frame_resolve, A, samples, f->d_counts, (const int*)f->d_kp);
+  HIPCHK(hipGetLastError());
+  unsigned long long counts[2] = {0, 0};  // (copied in stream order: one wait for the kernel and the counts)
+  HIPCHK(hipMemcpyAsync(counts, f->d_counts, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  double ms = 0.0;
+  for (size_t i = 0; i < f->used; ++i) {
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, f->events[i].first, f->events[i].second));
+    ms += t;
+  }
+  f->used = 0;
+  f->last.chunks_done = f->chunks_done;
+  f->last.samples_done = samples;
+  f->last.kernel_ms = ms;
+  f->last.nan_pixels = (int64_t)counts[0];
+  f->last.bytes_changed = (int64_t)counts[1];
+  return RT_OK;
+}
+
+// The frame's error summary over its `pixels` image pixels in `out` (may be null) and, when `d_se` is given,
+// its se map there in the frame's order (device memory). The ctx's device is selected; returns after the
+// stream is drained.
+int frame_error_run(rt_frame* f, double abs_tol, double rel_tol, double* d_se, long long pixels, rt_error_stats* out) {
+  rt_ctx* c = f->ctx;
+  const int blocks = (int)frame_grid(f).x;
+  if (!f->d_err) HIPCHK(hipMalloc((void**)&f->d_err, sizeof(unsigned long long) * (4 + (size_t)blocks)));
+  LaunchConst A{};
+  frame_const(f, A);
+  const int chunks = f->chunks_done, samples = frame_samples(f);
+  unsigned long long* d_acc = f->d_err;
+  double *d_block = reinterpret_cast<double*>(f->d_err + 4), *d_total = reinterpret_cast<double*>(f->d_err + 3);
+  HIPCHK(hipMemsetAsync(d_acc, 0, 4 * sizeof(unsigned long long), c->stream));
+  // (an adapted frame: each stopped pixel at its own (K_p, N_p))
+  FRAME_KERNEL_ADAPT(f, frame_error, A, (const double*)f->d_q, d_se, chunks, samples, abs_tol, rel_tol, d_acc,
+                     d_block, (const int*)f->d_kp);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(frame_error_sum, dim3(1), dim3(256), 0, c->stream, (const double*)d_block, blocks, d_total);
+  HIPCHK(hipGetLastError());
+  unsigned long long acc[4] = {0, 0, 0, 0};  // (copied in stream order: one wait for the kernels and the summary)
+  HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (out) {
+    rt_error_stats st{};
+    st.chunks_done = chunks;
+    st.samples_done = samples;
+    st.pixels = (int64_t)pixels;
+    st.nonfinite_pixels = (int64_t)acc[0];
+    st.unconverged_pixels = (int64_t)acc[1];
+    double total;
+    std::memcpy(&st.max_se, &acc[2], sizeof(double));
+    std::memcpy(&total, &acc[3], sizeof(double));
+    const int64_t finite = st.pixels - st.nonfinite_pixels;
+    st.mean_se = finite ? total / (double)(3 * finite) : 0.0;
+    *out = st;
+  }
+  return RT_OK;
+}
+
+// One of the frame's slab-order buffers (sums, moments) in image order, through the frame's kept stage
+// buffer, to the caller's host memory (an unsharded frame; the ctx's device is selected).
+int frame_image_out(rt_frame* f, const double* d_src, void* out) {
+  rt_ctx* c = f->ctx;
+  const size_t bytes = sizeof(double) * 3 * (size_t)f->npx;
+  if (!f->d_stage) HIPCHK(hipMalloc((void**)&f->d_stage, bytes));  // (kept: a checkpoint per step allocates once)
+  LaunchConst A{};
+  frame_const(f, A);
+  hipLaunchKernelGGL(assemble<double>, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream, d_src,
+                     f->d_stage, A.W, A.H, A.tile, A.tiles_x, 1, A.slab);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(out, f->d_stage, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
 }
 
 // A frame of `p` on c with zero sums and a zero previous preview, registered on the ctx; with
@@ -1436,10 +1557,8 @@ int frame_stop_call(rt_frame* f, const rt_adapt_rule* rule, const uint8_t* mask,
     HIPCHK(hipMemsetAsync(f->d_skip, 0, sizeof(unsigned long long) * words, c->stream));
   }
   LaunchConst A{};
-  long long per_shard;
-  fill_frame_geometry(A, &f->p, f->p.shard_rank, f->p.shard_count, per_shard);  // (unsharded: 0 of 1)
-  A.acc = f->d_sum;
-  int K = f->chunks_done, N = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
+  frame_const(f, A);
+  int K = f->chunks_done, N = frame_samples(f);
   unsigned long long* d_counts = f->d_adapt;
   HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
   const dim3 grid((unsigned)((f->slab + 255) / 256));
@@ -1468,6 +1587,49 @@ int frame_stop_call(rt_frame* f, const rt_adapt_rule* rule, const uint8_t* mask,
     st.stopped_now = (int64_t)counts[0];
     *out = st;
   }
+  return RT_OK;
+}
+
+// A frame restored from a version-1 blob and the caller's image-order moments (may be null): the blob's
+// checks, a new frame of the blob's parameters (a shard frame: `p`'s shard of them), then the payload and
+// the moments, the same size and order, each staged on the device and scattered into the frame's slab order.
+// An unsharded frame keeps the stage buffer for later saves; a shard frame keeps no image-order buffer.
+int frame_restore_run(rt_ctx* c, const void* buf, size_t len, const double* moments, bool shard, int shard_rank,
+                      int shard_count, const char* what, rt_frame** out) {
+  rt_frame_blob_desc b;
+  int rc = rt_frame_blob_info(buf, len, &b);
+  if (rc) return rc;
+  if (!c->has_scene) return state_error(std::string(what) + ": no scene uploaded");
+  if (b.scene_fingerprint != c->fingerprint || b.upload_flags != c->upload_flags)
+    return state_error(std::string(what) + ": the blob was saved over another scene (fingerprint or upload flags differ)");
+  rt_render_params p = b.params;  // (the blob's tile; the shard is the caller's: frame_new ignores it unsharded)
+  p.shard_rank = shard_rank;
+  p.shard_count = shard_count;
+  rt_frame* f = nullptr;
+  if ((rc = frame_new(c, &b.camera, &p, moments ? RT_FRAME_MOMENTS : 0u, what, &f, shard))) return rc;
+  auto fill = [&]() -> int {
+    DEVICE_SCOPE(c->device);
+    DevBuf tmp;  // (a shard frame's stage: the whole image, once per restore)
+    HIPCHK(hipMalloc(shard ? &tmp.p : (void**)&f->d_stage, (size_t)b.payload_bytes));
+    double* stage = shard ? (double*)tmp.p : f->d_stage;
+    LaunchConst A{};
+    frame_const(f, A);
+    const void* src[2] = {(const uint8_t*)buf + RT_FRAME_BLOB_HEADER, moments};
+    double* dst[2] = {f->d_sum, f->d_q};
+    for (int i = 0; i < (moments ? 2 : 1); ++i) {
+      HIPCHK(hipMemcpy(stage, src[i], (size_t)b.payload_bytes, hipMemcpyHostToDevice));
+      FRAME_KERNEL(f, frame_scatter, A, (const double*)stage, dst[i]);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return RT_OK;
+  };
+  if ((rc = fill())) {
+    rt_frame_close(f);
+    return rc;
+  }
+  f->chunks_done = b.chunks_done;
+  *out = f;
   return RT_OK;
 }
 
@@ -1540,42 +1702,7 @@ int rt_frame_resolve(rt_frame* f, uint8_t* out_rgb, double* out_lin, rt_frame_st
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
   // (nothing rendered since the last resolve: the device still holds that preview, and its stats repeat)
-  if (f->last.chunks_done != f->chunks_done) {
-    LaunchConst A{};
-    A.W = f->p.width;
-    A.H = f->p.height;
-    long long tt, ps, slab;
-    geometry(&f->p, A.tile, A.tiles_x, tt, ps, slab);
-    A.acc = f->d_sum;
-    A.out_rgb = f->d_rgb;
-    A.out_lin = f->d_lin;
-    int samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
-    unsigned long long* d_counts = f->d_counts;
-    HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    // (an adapted frame: each stopped pixel over its own N_p = min(spp, K_p * CH))
-    A.spp = f->p.spp;
-    A.chunk = f->chunk;
-    const int* d_kp = f->d_kp;
-    void* args[] = {&A, &samples, &d_counts, &d_kp};  // (frame_resolve takes the first three)
-    HIPCHK(hipLaunchKernel(d_kp ? (const void*)frame_resolve_adapt : (const void*)frame_resolve, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), args, 0,
-                           c->stream));
-    HIPCHK(hipGetLastError());
-    unsigned long long counts[2] = {0, 0};  // (copied in stream order: one wait for the kernel and the counts)
-    HIPCHK(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    double ms = 0.0;
-    for (size_t i = 0; i < f->used; ++i) {
-      float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, f->events[i].first, f->events[i].second));
-      ms += t;
-    }
-    f->used = 0;
-    f->last.chunks_done = f->chunks_done;
-    f->last.samples_done = samples;
-    f->last.kernel_ms = ms;
-    f->last.nan_pixels = (int64_t)counts[0];
-    f->last.bytes_changed = (int64_t)counts[1];
-  }
+  if (f->last.chunks_done != f->chunks_done && (rc = frame_resolve_run(f))) return rc;
   if (out_rgb) HIPCHK(hipMemcpy(out_rgb, f->d_rgb, (size_t)f->npx * 3, hipMemcpyDeviceToHost));
   if (out_lin) HIPCHK(hipMemcpy(out_lin, f->d_lin, sizeof(double) * (size_t)f->npx * 3, hipMemcpyDeviceToHost));
   if (out) *out = f->last;
@@ -1597,16 +1724,7 @@ int rt_frame_save(rt_frame* f, void* buf, size_t cap, size_t* out_len) {
   frame_write_header(f, (uint8_t*)buf);
   // the sums in image order (assemble's map at one shard), staged on the device, then copied out
   static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the blob's payload is copied as the host's doubles");
-  if (!f->d_stage) HIPCHK(hipMalloc((void**)&f->d_stage, payload));  // (kept: a checkpoint per step allocates once)
-  int tile, tiles_x;
-  long long tt, ps, slab;
-  geometry(&f->p, tile, tiles_x, tt, ps, slab);
-  hipLaunchKernelGGL(assemble<double>, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
-                     (const double*)f->d_sum, f->d_stage, f->p.width, f->p.height, tile, tiles_x, 1, slab);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy((uint8_t*)buf + RT_FRAME_BLOB_HEADER, f->d_stage, payload, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return frame_image_out(f, f->d_sum, (uint8_t*)buf + RT_FRAME_BLOB_HEADER);
 }
 
 int rt_frame_restore(rt_ctx* c, const void* buf, size_t len, rt_frame** out) {
@@ -1616,39 +1734,7 @@ int rt_frame_restore(rt_ctx* c, const void* buf, size_t len, rt_frame** out) {
 int rt_frame_restore_ex(rt_ctx* c, const void* buf, size_t len, const double* moments, rt_frame** out) {
   if (!c || !out) return invalid("rt_frame_restore: null argument");
   *out = nullptr;
-  rt_frame_blob_desc b;
-  int rc = rt_frame_blob_info(buf, len, &b);
-  if (rc) return rc;
-  if (!c->has_scene) return state_error("rt_frame_restore: no scene uploaded");
-  if (b.scene_fingerprint != c->fingerprint || b.upload_flags != c->upload_flags)
-    return state_error("rt_frame_restore: the blob was saved over another scene (fingerprint or upload flags differ)");
-  rt_frame* f = nullptr;
-  if ((rc = frame_new(c, &b.camera, &b.params, moments ? RT_FRAME_MOMENTS : 0u, "rt_frame_restore", &f))) return rc;
-  auto fill = [&]() -> int {
-    DEVICE_SCOPE(c->device);
-    HIPCHK(hipMalloc((void**)&f->d_stage, (size_t)b.payload_bytes));
-    int tile, tiles_x;
-    long long tt, ps, slab;
-    geometry(&f->p, tile, tiles_x, tt, ps, slab);
-    // the payload, then the caller's moments (the same size and order), each through the stage buffer
-    const void* src[2] = {(const uint8_t*)buf + RT_FRAME_BLOB_HEADER, moments};
-    double* dst[2] = {f->d_sum, f->d_q};
-    for (int i = 0; i < (moments ? 2 : 1); ++i) {
-      HIPCHK(hipMemcpy(f->d_stage, src[i], (size_t)b.payload_bytes, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(frame_scatter, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
-                         (const double*)f->d_stage, dst[i], f->p.width, f->p.height, tile, tiles_x);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return RT_OK;
-  };
-  if ((rc = fill())) {
-    rt_frame_close(f);
-    return rc;
-  }
-  f->chunks_done = b.chunks_done;
-  *out = f;
-  return RT_OK;
+  return frame_restore_run(c, buf, len, moments, false, 0, 1, "rt_frame_restore", out);
 }
 
 int rt_frame_moments(rt_frame* f, double* out_q) {
@@ -1660,17 +1746,7 @@ int rt_frame_moments(rt_frame* f, double* out_q) {
   if (f->chunks_done == 0) return state_error("rt_frame_moments: no chunk rendered yet");
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
-  const size_t bytes = sizeof(double) * 3 * (size_t)f->npx;
-  if (!f->d_stage) HIPCHK(hipMalloc((void**)&f->d_stage, bytes));
-  int tile, tiles_x;
-  long long tt, ps, slab;
-  geometry(&f->p, tile, tiles_x, tt, ps, slab);
-  hipLaunchKernelGGL(assemble<double>, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
-                     (const double*)f->d_q, f->d_stage, f->p.width, f->p.height, tile, tiles_x, 1, slab);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(out_q, f->d_stage, bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return frame_image_out(f, f->d_q, out_q);
 }
 
 int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_error_stats* out) {
@@ -1683,47 +1759,10 @@ int rt_frame_error(rt_frame* f, const rt_error_tol* tol, double* out_se, rt_erro
   if (f->chunks_done < 2) return state_error("rt_frame_error: the estimate needs at least 2 chunks");
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
-  const int blocks = (int)((f->npx + 255) / 256);
   const size_t map_bytes = sizeof(double) * 3 * (size_t)f->npx;
   if (out_se && !f->d_se) HIPCHK(hipMalloc((void**)&f->d_se, map_bytes));  // (kept, as d_stage is)
-  if (!f->d_err) HIPCHK(hipMalloc((void**)&f->d_err, sizeof(unsigned long long) * (4 + (size_t)blocks)));
-  int W = f->p.width, H = f->p.height, tile, tiles_x;
-  long long tt, ps, slab;
-  geometry(&f->p, tile, tiles_x, tt, ps, slab);
-  int chunks = f->chunks_done, samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
-  const double *d_sum = f->d_sum, *d_q = f->d_q;
-  double* d_se = out_se ? f->d_se : nullptr;
-  unsigned long long* d_acc = f->d_err;
-  double *d_block = reinterpret_cast<double*>(f->d_err + 4), *d_total = reinterpret_cast<double*>(f->d_err + 3);
-  HIPCHK(hipMemsetAsync(d_acc, 0, 4 * sizeof(unsigned long long), c->stream));
-  if (f->d_kp)  // (an adapted frame: each stopped pixel at its own (K_p, N_p))
-    hipLaunchKernelGGL(frame_error_adapt, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_sum, d_q, d_se, W, H, tile,
-                       tiles_x, chunks, samples, abs_tol, rel_tol, d_acc, d_block, (const int*)f->d_kp, f->chunk,
-                       f->p.spp);
-  else
-    hipLaunchKernelGGL(frame_error, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_sum, d_q, d_se, W, H, tile,
-                       tiles_x, chunks, samples, abs_tol, rel_tol, d_acc, d_block);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(frame_error_sum, dim3(1), dim3(256), 0, c->stream, (const double*)d_block, blocks, d_total);
-  HIPCHK(hipGetLastError());
-  unsigned long long acc[4] = {0, 0, 0, 0};  // (copied in stream order: one wait for the kernels and the summary)
-  HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((rc = frame_error_run(f, abs_tol, rel_tol, out_se ? f->d_se : nullptr, f->npx, out))) return rc;
   if (out_se) HIPCHK(hipMemcpy(out_se, f->d_se, map_bytes, hipMemcpyDeviceToHost));
-  if (out) {
-    rt_error_stats st{};
-    st.chunks_done = chunks;
-    st.samples_done = samples;
-    st.pixels = (int64_t)f->npx;
-    st.nonfinite_pixels = (int64_t)acc[0];
-    st.unconverged_pixels = (int64_t)acc[1];
-    double total;
-    std::memcpy(&st.max_se, &acc[2], sizeof(double));
-    std::memcpy(&total, &acc[3], sizeof(double));
-    const int64_t finite = st.pixels - st.nonfinite_pixels;
-    st.mean_se = finite ? total / (double)(3 * finite) : 0.0;
-    *out = st;
-  }
   return RT_OK;
 }
 
@@ -1752,11 +1791,9 @@ int rt_frame_chunk_counts(rt_frame* f, int32_t* out_chunks) {
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
   if (!f->d_kimg) HIPCHK(hipMalloc((void**)&f->d_kimg, sizeof(int) * (size_t)f->npx));
-  int tile, tiles_x;
-  long long tt, ps, slab;
-  geometry(&f->p, tile, tiles_x, tt, ps, slab);
-  hipLaunchKernelGGL(frame_chunk_counts, dim3((unsigned)((f->npx + 255) / 256)), dim3(256), 0, c->stream,
-                     (const int*)f->d_kp, f->d_kimg, f->p.width, f->p.height, tile, tiles_x, f->chunks_done);
+  LaunchConst A{};
+  frame_const(f, A);
+  FRAME_KERNEL(f, frame_chunk_counts, A, (const int*)f->d_kp, f->d_kimg, f->chunks_done);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpy(out_chunks, f->d_kimg, sizeof(int) * (size_t)f->npx, hipMemcpyDeviceToHost));
@@ -1780,35 +1817,7 @@ int rt_frame_resolve_shard(rt_frame* f, uint8_t* d_slab_rgb8, double* d_slab_lin
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
   // (nothing rendered since the last resolve: the frame still holds that preview, and its stats repeat)
-  if (f->last.chunks_done != f->chunks_done) {
-    LaunchConst A{};
-    shard_const(f, A);
-    A.out_rgb = f->d_rgb;
-    A.out_lin = f->d_lin;
-    int samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
-    unsigned long long* d_counts = f->d_counts;
-    HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    const int* d_kp = f->d_kp;
-    void* args[] = {&A, &samples, &d_counts, &d_kp};  // (frame_resolve_slab takes the first three)
-    HIPCHK(hipLaunchKernel(d_kp ? (const void*)frame_resolve_slab_adapt : (const void*)frame_resolve_slab,
-                           dim3((unsigned)((f->slab + 255) / 256)), dim3(256), args, 0, c->stream));
-    HIPCHK(hipGetLastError());
-    unsigned long long counts[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    double ms = 0.0;
-    for (size_t i = 0; i < f->used; ++i) {
-      float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, f->events[i].first, f->events[i].second));
-      ms += t;
-    }
-    f->used = 0;
-    f->last.chunks_done = f->chunks_done;
-    f->last.samples_done = samples;
-    f->last.kernel_ms = ms;
-    f->last.nan_pixels = (int64_t)counts[0];
-    f->last.bytes_changed = (int64_t)counts[1];
-  }
+  if (f->last.chunks_done != f->chunks_done && (rc = frame_resolve_run(f))) return rc;
   const size_t n3 = (size_t)f->slab * 3;
   if (d_slab_rgb8) HIPCHK(hipMemcpyAsync(d_slab_rgb8, f->d_rgb, n3, hipMemcpyDeviceToDevice, c->stream));
   if (d_slab_linear)
@@ -1829,42 +1838,7 @@ int rt_frame_error_shard(rt_frame* f, const rt_error_tol* tol, double* d_slab_se
   if (f->chunks_done < 2) return state_error("rt_frame_error_shard: the estimate needs at least 2 chunks");
   rt_ctx* c = f->ctx;
   DEVICE_SCOPE(c->device);
-  const int blocks = (int)((f->slab + 255) / 256);
-  if (!f->d_err) HIPCHK(hipMalloc((void**)&f->d_err, sizeof(unsigned long long) * (4 + (size_t)blocks)));
-  LaunchConst A{};
-  shard_const(f, A);
-  int chunks = f->chunks_done, samples = (int)std::min<long long>(f->p.spp, (long long)f->chunks_done * f->chunk);
-  unsigned long long* d_acc = f->d_err;
-  double *d_block = reinterpret_cast<double*>(f->d_err + 4), *d_total = reinterpret_cast<double*>(f->d_err + 3);
-  HIPCHK(hipMemsetAsync(d_acc, 0, 4 * sizeof(unsigned long long), c->stream));
-  if (f->d_kp)  // (an adapted frame: each stopped pixel at its own (K_p, N_p))
-    hipLaunchKernelGGL(frame_error_slab_adapt, dim3((unsigned)blocks), dim3(256), 0, c->stream, A,
-                       (const double*)f->d_q, d_slab_se, chunks, samples, abs_tol, rel_tol, d_acc, d_block,
-                       (const int*)f->d_kp);
-  else
-    hipLaunchKernelGGL(frame_error_slab, dim3((unsigned)blocks), dim3(256), 0, c->stream, A, (const double*)f->d_q,
-                       d_slab_se, chunks, samples, abs_tol, rel_tol, d_acc, d_block);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(frame_error_sum, dim3(1), dim3(256), 0, c->stream, (const double*)d_block, blocks, d_total);
-  HIPCHK(hipGetLastError());
-  unsigned long long acc[4] = {0, 0, 0, 0};
-  HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (out) {
-    rt_error_stats st{};
-    st.chunks_done = chunks;
-    st.samples_done = samples;
-    st.pixels = (int64_t)f->owned;
-    st.nonfinite_pixels = (int64_t)acc[0];
-    st.unconverged_pixels = (int64_t)acc[1];
-    double total;
-    std::memcpy(&st.max_se, &acc[2], sizeof(double));
-    std::memcpy(&total, &acc[3], sizeof(double));
-    const int64_t finite = st.pixels - st.nonfinite_pixels;
-    st.mean_se = finite ? total / (double)(3 * finite) : 0.0;
-    *out = st;
-  }
-  return RT_OK;
+  return frame_error_run(f, abs_tol, rel_tol, d_slab_se, f->owned, out);
 }
 
 int rt_frame_shard_state(rt_frame* f, double* d_slab_sums, double* d_slab_moments, int32_t* d_slab_chunks) {
@@ -1880,8 +1854,9 @@ int rt_frame_shard_state(rt_frame* f, double* d_slab_sums, double* d_slab_moment
   if (d_slab_sums) HIPCHK(hipMemcpyAsync(d_slab_sums, f->d_sum, bytes, hipMemcpyDeviceToDevice, c->stream));
   if (d_slab_moments) HIPCHK(hipMemcpyAsync(d_slab_moments, f->d_q, bytes, hipMemcpyDeviceToDevice, c->stream));
   if (d_slab_chunks) {
-    hipLaunchKernelGGL(frame_chunk_counts_slab, dim3((unsigned)((f->slab + 255) / 256)), dim3(256), 0, c->stream,
-                       (const int*)f->d_kp, (int*)d_slab_chunks, f->slab, f->chunks_done);
+    LaunchConst A{};
+    frame_const(f, A);
+    FRAME_KERNEL(f, frame_chunk_counts, A, (const int*)f->d_kp, (int*)d_slab_chunks, f->chunks_done);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1902,41 +1877,7 @@ int rt_frame_restore_shard(rt_ctx* c, const void* buf, size_t len, const double*
                            int shard_count, rt_frame** out) {
   if (!c || !out) return invalid("rt_frame_restore_shard: null argument");
   *out = nullptr;
-  rt_frame_blob_desc b;
-  int rc = rt_frame_blob_info(buf, len, &b);
-  if (rc) return rc;
-  if (!c->has_scene) return state_error("rt_frame_restore_shard: no scene uploaded");
-  if (b.scene_fingerprint != c->fingerprint || b.upload_flags != c->upload_flags)
-    return state_error("rt_frame_restore_shard: the blob was saved over another scene (fingerprint or upload flags differ)");
-  rt_render_params p = b.params;  // (the blob's tile; the shard is the caller's)
-  p.shard_rank = shard_rank;
-  p.shard_count = shard_count;
-  rt_frame* f = nullptr;
-  if ((rc = frame_new(c, &b.camera, &p, moments ? RT_FRAME_MOMENTS : 0u, "rt_frame_restore_shard", &f, true))) return rc;
-  auto fill = [&]() -> int {
-    DEVICE_SCOPE(c->device);
-    DevBuf stage;  // (the whole image, once per restore: a shard frame keeps no image-order buffer)
-    HIPCHK(hipMalloc(&stage.p, (size_t)b.payload_bytes));
-    LaunchConst A{};
-    shard_const(f, A);
-    const void* src[2] = {(const uint8_t*)buf + RT_FRAME_BLOB_HEADER, moments};
-    double* dst[2] = {f->d_sum, f->d_q};
-    for (int i = 0; i < (moments ? 2 : 1); ++i) {
-      HIPCHK(hipMemcpy(stage.p, src[i], (size_t)b.payload_bytes, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(frame_scatter_slab, dim3((unsigned)((f->slab + 255) / 256)), dim3(256), 0, c->stream, A,
-                         (const double*)stage.p, dst[i]);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return RT_OK;
-  };
-  if ((rc = fill())) {
-    rt_frame_close(f);
-    return rc;
-  }
-  f->chunks_done = b.chunks_done;
-  *out = f;
-  return RT_OK;
+  return frame_restore_run(c, buf, len, moments, true, shard_rank, shard_count, "rt_frame_restore_shard", out);
 }
 
 void rt_frame_close(rt_frame* f) {

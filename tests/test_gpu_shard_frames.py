@@ -13,6 +13,8 @@ Shapes (every test asserts its chunking first):
                                 tile 64, N 3: 2 tiles, the third shard owns nothing
     S2   256x192 spp 99  CH 5  20 chunks, depth 10, the last chunk of 4 samples
 """
+import json
+import os
 import socket
 
 import numpy as np
@@ -251,6 +253,36 @@ def test_shard_error_maps_and_stats(gpu_ctx, n, tile):
         assert 0 < merged["unconverged_pixels"] < merged["pixels"] - merged["nonfinite_pixels"]
     finally:
         close_all(frames)
+
+
+def test_mean_se_keeps_its_summation_order(gpu_ctx):
+    """mean_se to the last bit (the tests above hold it to 1e-12 only): a frame's blocks, one per 256 pixels of its
+    own order, and their fixed-order sum are what tests/golden/frame_mean_se.json recorded. An unsharded frame, its
+    3 shard frames at tile 16, and an adapted unsharded frame with pixels stopped before two chunks."""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "frame_mean_se.json")) as fh:
+        want = json.load(fh)
+    cam, p = setup(gpu_ctx, "cornell", P)
+    tol = (0.02, 0.05)
+    with gpu_ctx.open_frame(cam, p, moments=True) as fr:
+        fr.advance(9)
+        got = fr.error(*tol, want_map=False)[1]["mean_se"].hex()
+    assert got == want["cornell_97x61_40spp_depth8_seed77_9_chunks_tol_0.02_0.05"]
+    frames, _ = open_shards(gpu_ctx, cam, p, 3, 16, moments=True)
+    try:
+        advance_to(frames, 9)
+        assert [f.error_into(None, *tol)["mean_se"].hex() for f in frames] == want["the_same_on_3_shards_tile_16"]
+    finally:
+        close_all(frames)
+    gpu_ctx.upload(scene_of("three_spheres"))
+    cam = rtamd.camera("random_scene", 64, 48)
+    p = rtamd.make_params(64, 48, 6, 8, rtamd.RT_RNG_PHILOX, seed=77)
+    yy, xx = np.mgrid[0:48, 0:64]
+    with gpu_ctx.open_frame(cam, p, moments=True) as fr:
+        fr.advance(1)
+        fr.stop((xx + yy) % 5 == 0)
+        fr.advance(2)
+        got = fr.error(want_map=False)[1]["mean_se"].hex()
+    assert got == want["three_spheres_64x48_6spp_depth8_seed77_stop_mask_at_1_chunk_error_at_3"]
 
 
 # ----------------------------------------------------------------------------- 4. adaptive
