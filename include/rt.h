@@ -598,7 +598,8 @@ int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
  *             rt_frame_moments wrote them when the blob was saved): a tracked frame that continues exactly
  *             where the saved one stopped. moments == NULL: rt_frame_restore (an untracked frame). The
  *             version-1 blob has no room for Q and is unchanged; keeping a blob and its moments together
- *             is the caller's responsibility (moments of another save give a frame whose Q is not rt.h's).
+ *             is the caller's responsibility (moments of another save give a frame whose Q is not rt.h's);
+ *             a checkpoint (below) holds both.
  * error       The error map and its summary at any point of a tracked frame with chunks_done >= 2, at a
  *             tolerance (NULL: {0, 0}; a negative or NaN value: RT_E_INVALID). out_se (H*W*3 doubles, image
  *             order) and out may each be NULL. RT_E_STATE for an untracked frame, a frame whose ctx's
@@ -646,7 +647,8 @@ int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
  *             `out` may be NULL.
  * chunk_counts K_p per pixel, H*W int32 in image order (an active pixel: chunks_done).
  * save        rt_frame_save on a frame with any stopped pixel returns RT_E_STATE: the version-1 blob has no
- *             room for K_p and stays as it is. rt_frame_moments still works on an adapted frame.
+ *             room for K_p and stays as it is (rt_frame_checkpoint, below, saves such a frame).
+ *             rt_frame_moments still works on an adapted frame.
  * rt_adapt_decide  The same per-pixel rule on the host alone (no device), over image-order arrays (a blob's
  *             payload and the saved moments at `chunks_done` chunks of a frame of chunk size `chunk`):
  *             chunks_out[i] = chunks_in[i] where that is nonzero (already stopped), chunks_done where the
@@ -706,14 +708,68 @@ int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
  *                return RT_E_STATE on a shard frame (the message names the call to use); resolve_shard,
  *                error_shard and shard_state return RT_E_STATE on an unsharded frame.
  *
+ * Checkpoints: the version-2 blob, which carries a tracked frame's Q and an adapted frame's K_p with the sums,
+ * so that any frame can be interrupted and continued. The version-1 calls above are unchanged: rt_frame_save
+ * writes and rt_frame_restore* and rt_frame_blob_info take version 1 only. Layout, little-endian,
+ * RT_FRAME_CKPT_HEADER = 320 bytes of header, then the payload:
+ *     0..287   the version-1 header, field for field, with version = 2 (RT_FRAME_CKPT_VERSION); the u64 at 280 =
+ *              the bytes that follow offset 320
+ *   288  u32   sections: RT_CKPT_MOMENTS (1) | RT_CKPT_STOPS (2); any other bit is invalid
+ *   292  28 bytes reserved, all zero (a nonzero byte is invalid)
+ *   320        S  pixels * 3 f64, image order (as version 1)
+ *              Q  pixels * 3 f64, image order, only with RT_CKPT_MOMENTS
+ *              K  pixels * i32, image order, only with RT_CKPT_STOPS: 0 = an active pixel, else K_p in
+ *                 [1, chunks_done]
+ * K stores 0 for an active pixel, unlike rt_frame_chunk_counts, whose chunks_done for an active pixel cannot be
+ * told from a pixel stopped at the current chunks_done. The header holds no counts: every shard of an image
+ * writes the same bytes.
+ * checkpoint_info  (host only) Parses and validates a version-1 or version-2 blob. desc.blob is
+ *             rt_frame_blob_info's descriptor (payload_bytes = the bytes after the blob's own header); a
+ *             version-1 blob has sections 0. sums_offset, moments_offset and stops_offset are byte offsets
+ *             from the start of the blob (0: the section is absent). stopped_pixels (K != 0), stopped_nan
+ *             (those whose S has a NaN channel) and active_pixels are counted by scanning the payload. Checks:
+ *             every version-1 rule, the section bits, the reserved bytes, payload bytes = pixels *
+ *             (24 + 24 [Q] + 4 [K]), length = 320 + payload bytes, every K in [0, chunks_done]. Else RT_E_INVALID.
+ * checkpoint_resolve  (host only) The preview rt_frame_resolve gives of that state, by the device's arithmetic:
+ *             per pixel S / N_p, N_p = min(spp, K_p * CH) for a stopped pixel, else the frame's samples_done,
+ *             then albedoToColor. out_rgb8 (H*W*3 bytes), out_linear (H*W*3 doubles) and out may each be NULL.
+ *             nan_pixels is exact, bytes_changed is taken against an all-zero image, kernel_ms is 0.
+ *             RT_E_INVALID for a malformed blob or chunks_done = 0.
+ * checkpoint_error  (host only) rt_frame_error's map and summary of that state, per pixel at (K_p, N_p) by
+ *             rt_error.h's function; mean_se is the sequential sum in pixel and channel order. RT_E_INVALID for a
+ *             malformed blob, one without RT_CKPT_MOMENTS, chunks_done < 2 or a bad tolerance.
+ * checkpoint  rt_frame_save's buffer protocol on an unsharded frame; always version 2. RT_CKPT_MOMENTS is set if
+ *             and only if the frame tracks moments, RT_CKPT_STOPS if and only if at least one pixel is stopped
+ *             (when rt_frame_save refuses). With sections 0 the blob is rt_frame_save's apart from the version
+ *             word and the 32 further header bytes. RT_E_STATE on a shard frame.
+ * resume      A new frame from a version-1 or version-2 blob: the saved frame. It tracks moments if and only if
+ *             the blob has Q, and has stopped pixels if and only if the blob has K with a nonzero entry. Any
+ *             further sequence of advance, adapt, stop, resolve, error, moments, chunk_counts and checkpoint calls
+ *             gives, bit for bit and count for count, what the uninterrupted frame gives (but the first resolve's
+ *             bytes_changed is taken against zero, as for every restored frame). Errors as rt_frame_restore.
+ * resume_shard  The same as a shard frame (shard_rank of shard_count, the tile being the blob's): only the owned
+ *             pixels are taken, so a checkpoint of N shards resumes on M, or unsharded.
+ * shard_stops The raw K_p of a shard frame (0 = active) in slab order into device memory, slab_pixels int32: all
+ *             zeros before any stop call; padding slots unspecified. RT_E_STATE on an unsharded frame.
+ * checkpoint_header  The 320 header bytes of the whole image's checkpoint (cap >= RT_FRAME_CKPT_HEADER, else
+ *             RT_E_INVALID), the shard fields written as 0 / 1. `sections` is the caller's, the OR over the
+ *             image's shards (unknown bits: RT_E_INVALID; RT_CKPT_MOMENTS on an untracked frame: RT_E_STATE).
+ *             `chunks_done` is the image's (-1: the frame's own): a shard whose pixels are all stopped may lag
+ *             behind the others, so a value above the frame's own is accepted when the frame has no active
+ *             pixel (else RT_E_STATE); a value below the frame's own or above chunks_total is RT_E_INVALID.
+ *             Header + assembled S + assembled Q + merged K is the unsharded frame's checkpoint byte for byte.
+ *
  * Not covered: frames spanning the devices of an rt_create_multi ctx (a shard frame acts on one device; the
- * caller gathers), reactivating a stopped pixel, adaptive one-shot rt_render, saving an adapted frame (no blob
- * version carries K_p or Q), compacting a mostly stopped frame's work-items, error estimates and adaptive
- * sampling for tier A, and extending a frame past its spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its
- * per-chunk meaning.
+ * caller gathers), reactivating a stopped pixel, adaptive one-shot rt_render, compacting a mostly stopped
+ * frame's work-items, error estimates and adaptive sampling for tier A, a checksum over a blob's payload, and
+ * extending a frame past its spp (CH depends on spp). RT_FLAG_NAN_CULL keeps its per-chunk meaning.
  */
 #define RT_FRAME_BLOB_VERSION 1u
 #define RT_FRAME_BLOB_HEADER 288
+#define RT_FRAME_CKPT_VERSION 2u
+#define RT_FRAME_CKPT_HEADER 320
+#define RT_CKPT_MOMENTS 1u /* the checkpoint has Q */
+#define RT_CKPT_STOPS 2u   /* the checkpoint has K */
 typedef struct rt_frame rt_frame;
 typedef struct rt_frame_stats {
     int32_t chunk;
@@ -798,6 +854,27 @@ int rt_frame_shard_state(rt_frame* f, double* d_slab_sums, double* d_slab_moment
 int rt_frame_save_header(rt_frame* f, void* buf, size_t cap);
 int rt_frame_restore_shard(rt_ctx* ctx, const void* buf, size_t len, const double* moments, int shard_rank,
                            int shard_count, rt_frame** out);
+/* Checkpoints (above): the version-2 blob. */
+typedef struct rt_frame_ckpt_desc {
+    rt_frame_blob_desc blob; /* version 1 or 2; payload_bytes = the bytes after the blob's own header */
+    uint32_t sections;
+    uint32_t _pad;
+    uint64_t sums_offset;
+    uint64_t moments_offset; /* 0: no Q */
+    uint64_t stops_offset;   /* 0: no K */
+    int64_t stopped_pixels;
+    int64_t stopped_nan;
+    int64_t active_pixels;
+} rt_frame_ckpt_desc; /* 344 bytes */
+int rt_frame_checkpoint_info(const void* buf, size_t len, rt_frame_ckpt_desc* out);
+int rt_checkpoint_resolve(const void* buf, size_t len, uint8_t* out_rgb8, double* out_linear, rt_frame_stats* out);
+int rt_checkpoint_error(const void* buf, size_t len, const rt_error_tol* tol, double* out_se, rt_error_stats* out);
+int rt_frame_checkpoint(rt_frame* f, void* buf, size_t cap, size_t* out_len);
+int rt_frame_resume(rt_ctx* ctx, const void* buf, size_t len, rt_frame** out);
+int rt_frame_resume_shard(rt_ctx* ctx, const void* buf, size_t len, int shard_rank, int shard_count,
+                          rt_frame** out);
+int rt_frame_shard_stops(rt_frame* f, int32_t* d_slab_stops);
+int rt_frame_checkpoint_header(rt_frame* f, uint32_t sections, int chunks_done, void* buf, size_t cap);
 /* The fingerprint rt_upload_scene records for a descriptor (host only; the blob's field at 272). */
 int rt_scene_fingerprint(const rt_scene_desc* desc, uint64_t* out);
 /* The chunking of a tier-B frame of `pixels` pixels at `spp` samples (host only): *out_chunk =

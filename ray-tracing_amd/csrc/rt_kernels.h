@@ -1183,6 +1183,33 @@ __global__ void __launch_bounds__(256) frame_stop_mask(LaunchConst A, int* kp, u
   adapt_body<false>(A, nullptr, kp, skip, mask, K, 0, rt_adapt_rule{}, counts);
 }
 
+// An adaptive frame's stops put back from a checkpoint (rt_frame_resume*): one thread per slab pixel in both
+// kinds of frame, as adapt_body, so that a wave is one word of the skip bitmask. A thread reads its pixel's
+// saved K_p (`stops`: the whole image, image order, 0 = active) into kp, and the wave's lane 0 writes the word
+// from one ballot of "stopped". The sums (A.acc) have been scattered before: counts[0] += stopped pixels,
+// counts[1] += those of them whose sum has a NaN channel (block_add2). Padding slots: never set, never counted
+// (kp is zeroed beforehand).
+__global__ void __launch_bounds__(256) frame_restore_stops(LaunchConst A, const int* stops, int* kp,
+                                                           unsigned long long* skip, unsigned long long* counts) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool stopped = false, nan = false;
+  long long slot, img;
+  if (frame_pixel<true>(A, idx, slot, img)) {
+    const int k = stops[img];
+    kp[idx] = k;
+    stopped = k != 0;
+    if (stopped) {
+      const double s[3] = {A.acc[idx * 3], A.acc[idx * 3 + 1], A.acc[idx * 3 + 2]};
+      nan = s[0] != s[0] || s[1] != s[1] || s[2] != s[2];
+    }
+  }
+  const unsigned long long word = __ballot(stopped);
+  const unsigned n_stopped = (unsigned)__popcll(word), n_nan = (unsigned)__popcll(__ballot(nan));
+  // (the slab is whole 8x8 blocks: a wave is inside it or past it)
+  if ((threadIdx.x & 63) == 0 && idx < A.slab) skip[idx >> 6] = word;
+  block_add2(n_stopped, n_nan, counts);
+}
+
 // ---------------------------------------------------------------- debug: closest hits
 template <unsigned F, bool PK = false>
 __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* rays, int n, double tmin,

@@ -1335,7 +1335,7 @@ int frame_kind(const rt_frame* f, bool shard, const char* what, const char* inst
 
 // The header of the frame's whole-image version-1 blob (rt.h): a shard frame's is the unsharded frame's,
 // its shard fields written as 0 / 1.
-void frame_write_header(const rt_frame* f, uint8_t* buf) {
+rt_frame_blob_desc frame_blob_desc(const rt_frame* f) {
   rt_frame_blob_desc b{};
   b.version = RT_FRAME_BLOB_VERSION;
   b.upload_flags = f->ctx->upload_flags;
@@ -1348,7 +1348,13 @@ void frame_write_header(const rt_frame* f, uint8_t* buf) {
   b.pixels = f->npx;
   b.scene_fingerprint = f->ctx->fingerprint;
   b.payload_bytes = sizeof(double) * 3 * (size_t)f->npx;
-  rt::blob_write_header(b, buf);
+  return b;
+}
+void frame_write_header(const rt_frame* f, uint8_t* buf) { rt::blob_write_header(frame_blob_desc(f), buf); }
+
+// The sections of the frame's own checkpoint (rt.h): Q when it tracks moments, K when a pixel is stopped.
+uint32_t frame_sections(const rt_frame* f) {
+  return (f->d_q ? RT_CKPT_MOMENTS : 0u) | (f->stopped_nan + f->stopped_other > 0 ? RT_CKPT_STOPS : 0u);
 }
 
 // The frame's geometry and sums in launch constants, for its frame_* helper kernels (rt_kernels.h): the
@@ -1590,15 +1596,17 @@ int frame_stop_call(rt_frame* f, const rt_adapt_rule* rule, const uint8_t* mask,
   return RT_OK;
 }
 
-// A frame restored from a version-1 blob and the caller's image-order moments (may be null): the blob's
-// checks, a new frame of the blob's parameters (a shard frame: `p`'s shard of them), then the payload and
-// the moments, the same size and order, each staged on the device and scattered into the frame's slab order.
-// An unsharded frame keeps the stage buffer for later saves; a shard frame keeps no image-order buffer.
-int frame_restore_run(rt_ctx* c, const void* buf, size_t len, const double* moments, bool shard, int shard_rank,
-                      int shard_count, const char* what, rt_frame** out) {
-  rt_frame_blob_desc b;
-  int rc = rt_frame_blob_info(buf, len, &b);
-  if (rc) return rc;
+// A frame from a parsed blob `b` (either version), its image-order sums and image-order moments (may be null:
+// an untracked frame), in the caller's memory: the scene checks, a new frame of the blob's parameters (a shard
+// frame: `p`'s shard of them), then the sums and the moments, the same size and order, each staged on the
+// device and scattered into the frame's slab order. An unsharded frame keeps the stage buffer for later
+// saves; a shard frame keeps no image-order buffer.
+// `stops` (a version-2 checkpoint's K section with a nonzero entry, image order like the other two; else null)
+// makes the frame an adapted one: K_p and the skip bitmask are allocated as a first stop call allocates them,
+// K is staged the same way, and frame_restore_stops fills both and counts the stopped pixels by their sums.
+int frame_from(rt_ctx* c, const rt_frame_blob_desc& b, const void* sums, const void* moments, const void* stops,
+               bool shard, int shard_rank, int shard_count, const char* what, rt_frame** out) {
+  int rc;
   if (!c->has_scene) return state_error(std::string(what) + ": no scene uploaded");
   if (b.scene_fingerprint != c->fingerprint || b.upload_flags != c->upload_flags)
     return state_error(std::string(what) + ": the blob was saved over another scene (fingerprint or upload flags differ)");
@@ -1609,19 +1617,38 @@ int frame_restore_run(rt_ctx* c, const void* buf, size_t len, const double* mome
   if ((rc = frame_new(c, &b.camera, &p, moments ? RT_FRAME_MOMENTS : 0u, what, &f, shard))) return rc;
   auto fill = [&]() -> int {
     DEVICE_SCOPE(c->device);
+    const size_t bytes = sizeof(double) * 3 * (size_t)b.pixels;
     DevBuf tmp;  // (a shard frame's stage: the whole image, once per restore)
-    HIPCHK(hipMalloc(shard ? &tmp.p : (void**)&f->d_stage, (size_t)b.payload_bytes));
+    HIPCHK(hipMalloc(shard ? &tmp.p : (void**)&f->d_stage, bytes));
     double* stage = shard ? (double*)tmp.p : f->d_stage;
     LaunchConst A{};
     frame_const(f, A);
-    const void* src[2] = {(const uint8_t*)buf + RT_FRAME_BLOB_HEADER, moments};
+    const void* src[2] = {sums, moments};
     double* dst[2] = {f->d_sum, f->d_q};
     for (int i = 0; i < (moments ? 2 : 1); ++i) {
-      HIPCHK(hipMemcpy(stage, src[i], (size_t)b.payload_bytes, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(stage, src[i], bytes, hipMemcpyHostToDevice));
       FRAME_KERNEL(f, frame_scatter, A, (const double*)stage, dst[i]);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(c->stream));
     }
+    if (!stops) return RT_OK;
+    const size_t words = (size_t)(f->slab / 64);  // (the slab is whole 8x8 blocks)
+    HIPCHK(hipMalloc((void**)&f->d_adapt, 2 * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void**)&f->d_kp, sizeof(int) * (size_t)f->slab));
+    HIPCHK(hipMalloc((void**)&f->d_skip, sizeof(unsigned long long) * words));
+    HIPCHK(hipMemsetAsync(f->d_adapt, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(f->d_kp, 0, sizeof(int) * (size_t)f->slab, c->stream));
+    HIPCHK(hipMemsetAsync(f->d_skip, 0, sizeof(unsigned long long) * words, c->stream));
+    // (K is a sixth of a sums section's bytes: the same stage holds it; the scatters above are drained)
+    HIPCHK(hipMemcpy(stage, stops, sizeof(int) * (size_t)b.pixels, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(frame_restore_stops, dim3((unsigned)((f->slab + 255) / 256)), dim3(256), 0, c->stream, A,
+                       (const int*)stage, f->d_kp, f->d_skip, f->d_adapt);
+    HIPCHK(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(counts, f->d_adapt, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    f->stopped_nan = (long long)counts[1];
+    f->stopped_other = (long long)(counts[0] - counts[1]);
     return RT_OK;
   };
   if ((rc = fill())) {
@@ -1631,6 +1658,26 @@ int frame_restore_run(rt_ctx* c, const void* buf, size_t len, const double* mome
   f->chunks_done = b.chunks_done;
   *out = f;
   return RT_OK;
+}
+
+int frame_restore_run(rt_ctx* c, const void* buf, size_t len, const double* moments, bool shard, int shard_rank,
+                      int shard_count, const char* what, rt_frame** out) {
+  rt_frame_blob_desc b;
+  int rc = rt_frame_blob_info(buf, len, &b);
+  if (rc) return rc;
+  return frame_from(c, b, (const uint8_t*)buf + RT_FRAME_BLOB_HEADER, moments, nullptr, shard, shard_rank, shard_count,
+                    what, out);
+}
+
+// rt_frame_resume*: a frame from a version-1 or version-2 blob, with the sections it has.
+int frame_resume_run(rt_ctx* c, const void* buf, size_t len, bool shard, int shard_rank, int shard_count,
+                     const char* what, rt_frame** out) {
+  rt_frame_ckpt_desc d;
+  int rc = rt_frame_checkpoint_info(buf, len, &d);
+  if (rc) return rc;
+  const uint8_t* in = (const uint8_t*)buf;
+  return frame_from(c, d.blob, in + d.sums_offset, d.moments_offset ? in + d.moments_offset : nullptr,
+                    d.stopped_pixels > 0 ? in + d.stops_offset : nullptr, shard, shard_rank, shard_count, what, out);
 }
 
 }  // namespace
@@ -1878,6 +1925,93 @@ int rt_frame_restore_shard(rt_ctx* c, const void* buf, size_t len, const double*
   if (!c || !out) return invalid("rt_frame_restore_shard: null argument");
   *out = nullptr;
   return frame_restore_run(c, buf, len, moments, true, shard_rank, shard_count, "rt_frame_restore_shard", out);
+}
+
+// ---- checkpoints (rt.h): the version-2 blob, with a tracked frame's Q and an adapted frame's K_p
+
+int rt_frame_checkpoint(rt_frame* f, void* buf, size_t cap, size_t* out_len) {
+  int rc = frame_live(f, "rt_frame_checkpoint");
+  if (rc) return rc;
+  if ((rc = frame_kind(f, false, "rt_frame_checkpoint",
+                       "rt_frame_checkpoint_header, rt_frame_shard_state and rt_frame_shard_stops")))
+    return rc;
+  const uint32_t sections = frame_sections(f);
+  const size_t need = RT_FRAME_CKPT_HEADER + (size_t)rt::ckpt_payload_bytes(f->npx, sections);
+  if (out_len) *out_len = need;
+  if (!buf || cap < need) return RT_OK;  // (size query)
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  uint8_t* at = (uint8_t*)buf;
+  rt::ckpt_write_header(frame_blob_desc(f), sections, at);
+  at += RT_FRAME_CKPT_HEADER;
+  const size_t bytes = sizeof(double) * 3 * (size_t)f->npx;
+  // S and Q in image order as rt_frame_save and rt_frame_moments write them, then the raw K_p (0 = active)
+  if ((rc = frame_image_out(f, f->d_sum, at))) return rc;
+  at += bytes;
+  if (sections & RT_CKPT_MOMENTS) {
+    if ((rc = frame_image_out(f, f->d_q, at))) return rc;
+    at += bytes;
+  }
+  if (sections & RT_CKPT_STOPS) {
+    if (!f->d_kimg) HIPCHK(hipMalloc((void**)&f->d_kimg, sizeof(int) * (size_t)f->npx));
+    LaunchConst A{};
+    frame_const(f, A);
+    FRAME_LAUNCH(f, frame_chunk_counts<false>, A, (const int*)f->d_kp, f->d_kimg, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(at, f->d_kimg, sizeof(int) * (size_t)f->npx, hipMemcpyDeviceToHost));
+  }
+  return RT_OK;
+}
+
+int rt_frame_resume(rt_ctx* c, const void* buf, size_t len, rt_frame** out) {
+  if (!c || !out) return invalid("rt_frame_resume: null argument");
+  *out = nullptr;
+  return frame_resume_run(c, buf, len, false, 0, 1, "rt_frame_resume", out);
+}
+
+int rt_frame_resume_shard(rt_ctx* c, const void* buf, size_t len, int shard_rank, int shard_count, rt_frame** out) {
+  if (!c || !out) return invalid("rt_frame_resume_shard: null argument");
+  *out = nullptr;
+  return frame_resume_run(c, buf, len, true, shard_rank, shard_count, "rt_frame_resume_shard", out);
+}
+
+int rt_frame_shard_stops(rt_frame* f, int32_t* d_slab_stops) {
+  int rc = frame_live(f, "rt_frame_shard_stops");
+  if (rc) return rc;
+  if ((rc = frame_kind(f, true, "rt_frame_shard_stops", "rt_frame_checkpoint"))) return rc;
+  if (!d_slab_stops) return invalid("rt_frame_shard_stops: null argument");
+  rt_ctx* c = f->ctx;
+  DEVICE_SCOPE(c->device);
+  if (!f->d_kp) {  // (no stop call yet: every pixel is active)
+    HIPCHK(hipMemsetAsync(d_slab_stops, 0, sizeof(int) * (size_t)f->slab, c->stream));
+  } else {
+    LaunchConst A{};
+    frame_const(f, A);
+    FRAME_LAUNCH(f, frame_chunk_counts<true>, A, (const int*)f->d_kp, (int*)d_slab_stops, 0);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_frame_checkpoint_header(rt_frame* f, uint32_t sections, int chunks_done, void* buf, size_t cap) {
+  int rc = frame_live(f, "rt_frame_checkpoint_header");
+  if (rc) return rc;
+  if (!buf || cap < RT_FRAME_CKPT_HEADER)
+    return invalid("rt_frame_checkpoint_header: needs a buffer of RT_FRAME_CKPT_HEADER bytes");
+  if (sections & ~(RT_CKPT_MOMENTS | RT_CKPT_STOPS)) return invalid("rt_frame_checkpoint_header: unknown section bit");
+  if ((sections & RT_CKPT_MOMENTS) && !f->d_q)
+    return state_error("rt_frame_checkpoint_header: RT_CKPT_MOMENTS on a frame opened without RT_FRAME_MOMENTS");
+  if (chunks_done == -1) chunks_done = f->chunks_done;
+  if (chunks_done < f->chunks_done || chunks_done > f->chunks_total)
+    return invalid("rt_frame_checkpoint_header: chunks_done must be -1 or in [the frame's own, chunks_total]");
+  if (chunks_done > f->chunks_done && f->stopped_nan + f->stopped_other != f->owned)
+    return state_error("rt_frame_checkpoint_header: chunks_done is ahead of a frame that still has active pixels");
+  rt_frame_blob_desc b = frame_blob_desc(f);
+  b.chunks_done = chunks_done;
+  rt::ckpt_write_header(b, sections, (uint8_t*)buf);
+  return RT_OK;
 }
 
 void rt_frame_close(rt_frame* f) {

@@ -37,6 +37,8 @@ RT_UPLOAD_REFERENCE_BVH = 1
 RT_ADAPT_NAN = 1        # rt_frame_adapt: stop pixels whose running sum has a NaN channel
 RT_ADAPT_CONVERGED = 2  # ... and finite pixels converged under (abs_tol, rel_tol)
 RT_FRAME_MOMENTS = 1  # rt_frame_open_ex: keep the chunk sums' second moments (per-pixel error estimates)
+RT_CKPT_MOMENTS = 1  # a version-2 checkpoint's sections: it has Q ...
+RT_CKPT_STOPS = 2    # ... it has K (0 = active, else the pixel's K_p)
 RT_DEBUG_RESUMABLE = 4  # rt_debug_closest_hits: the render loop's resumable binary walk
 RT_DEBUG_WIDE = 8       # rt_debug_closest_hits: the resumable walk over the 4-wide fp32-box tree
 RT_DEBUG_QNODE = 16     # ... over its quantised form (rt_qnode) with sphere quadruples (spheres-only worlds)
@@ -160,6 +162,13 @@ class rt_adapt_stats(C.Structure):
                 ("stopped_nan", C.c_int64), ("stopped_converged_or_masked", C.c_int64), ("stopped_now", C.c_int64)]
 
 
+class rt_frame_ckpt_desc(C.Structure):
+    _fields_ = [("blob", rt_frame_blob_desc), ("sections", C.c_uint32), ("_pad", C.c_uint32),
+                ("sums_offset", C.c_uint64), ("moments_offset", C.c_uint64), ("stops_offset", C.c_uint64),
+                ("stopped_pixels", C.c_int64), ("stopped_nan", C.c_int64), ("active_pixels", C.c_int64)]
+
+
+assert C.sizeof(rt_frame_ckpt_desc) == 344
 assert C.sizeof(rt_error_tol) == 16 and C.sizeof(rt_error_stats) == 48
 assert C.sizeof(rt_adapt_rule) == 24 and C.sizeof(rt_adapt_stats) == 48
 assert C.sizeof(rt_node) == 64 and C.sizeof(rt_material) == 16 and C.sizeof(rt_texture) == 48
@@ -186,6 +195,8 @@ EXPORTED = [
     "rt_frame_adapt", "rt_frame_stop", "rt_frame_chunk_counts", "rt_adapt_decide",
     "rt_frame_open_shard", "rt_frame_resolve_shard", "rt_frame_error_shard", "rt_error_stats_merge",
     "rt_frame_shard_state", "rt_frame_save_header", "rt_frame_restore_shard", "rt_debug_wide_keys",
+    "rt_frame_checkpoint_info", "rt_checkpoint_resolve", "rt_checkpoint_error", "rt_frame_checkpoint",
+    "rt_frame_resume", "rt_frame_resume_shard", "rt_frame_shard_stops", "rt_frame_checkpoint_header",
 ]
 
 # include/rt_wide.h: one 4-wide node (128 B)
@@ -301,6 +312,14 @@ def lib() -> C.CDLL:
             "rt_frame_shard_state": (I, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             "rt_frame_save_header": (I, [C.c_void_p, C.c_char_p, C.c_size_t]),
             "rt_frame_restore_shard": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(D), I, I, P(C.c_void_p)]),
+            "rt_frame_checkpoint_info": (I, [C.c_char_p, C.c_size_t, P(rt_frame_ckpt_desc)]),
+            "rt_checkpoint_resolve": (I, [C.c_char_p, C.c_size_t, P(C.c_uint8), P(D), P(rt_frame_stats)]),
+            "rt_checkpoint_error": (I, [C.c_char_p, C.c_size_t, P(rt_error_tol), P(D), P(rt_error_stats)]),
+            "rt_frame_checkpoint": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_size_t)]),
+            "rt_frame_resume": (I, [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_void_p)]),
+            "rt_frame_resume_shard": (I, [C.c_void_p, C.c_char_p, C.c_size_t, I, I, P(C.c_void_p)]),
+            "rt_frame_shard_stops": (I, [C.c_void_p, C.c_void_p]),
+            "rt_frame_checkpoint_header": (I, [C.c_void_p, C.c_uint32, I, C.c_char_p, C.c_size_t]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -673,6 +692,15 @@ class Context:
         tile is the blob's; `moments` is image order, as for `restore_frame`)."""
         return restore_shard_frame(self, blob, rank, count, moments)
 
+    def resume_frame(self, blob: bytes) -> "ProgressiveFrame":
+        """rt_frame_resume: the frame a checkpoint (`ProgressiveFrame.checkpoint`, version 2) or a version-1
+        blob holds, with its moments and its stopped pixels, to be continued on this ctx."""
+        return resume_frame(self, blob)
+
+    def resume_shard_frame(self, blob: bytes, rank: int, count: int) -> "ShardFrame":
+        """rt_frame_resume_shard: shard `rank` of `count` of the frame a whole-image checkpoint holds."""
+        return resume_shard_frame(self, blob, rank, count)
+
     def render(self, cam: rt_camera, params: rt_render_params, col_gens: Optional[np.ndarray] = None,
                linear: bool = False, want_gens: bool = False):
         """Full image, blocking. Returns (rgb8[H,W,3], linear[H,W,3] | None, gens[W,2] | None)."""
@@ -913,5 +941,6 @@ def assemble_host(slabs: np.ndarray, params: rt_render_params) -> np.ndarray:
 
 
 from .progressive import (ProgressiveFrame, ShardFrame, ShardedProgressiveFrame, adapt_decide,  # noqa: E402
-                          blob_info, error_estimate, error_stats_merge, render_progressive, restore_frame,
-                          restore_shard_frame)
+                          blob_info, checkpoint_error, checkpoint_info, checkpoint_resolve, error_estimate,
+                          error_stats_merge, render_progressive, restore_frame, restore_shard_frame, resume_frame,
+                          resume_shard_frame)

@@ -22,6 +22,11 @@ Shard frames (rt.h): `ctx.open_shard_frame(cam, params)` is the same frame over 
 (params.tile, shard_rank, shard_count), its previews, error map and state left in slab order in device memory
 (`ShardFrame`); `ShardedProgressiveFrame` drives `world` of them, in one process or as one rank of a
 torch.distributed group, and gives the unsharded frame's results bit for bit.
+
+Checkpoints (rt.h, the version-2 blob): `fr.checkpoint()` is one blob with the sums, a tracked frame's moments
+and an adapted frame's K_p; `ctx.resume_frame(blob)` / `ctx.resume_shard_frame(blob, rank, count)` continue it
+bit for bit, on any shard count; `checkpoint_info`, `checkpoint_resolve` and `checkpoint_error` parse, preview
+and estimate a checkpoint on the host alone; `render_progressive(..., resume=blob, checkpoint=callable)`.
 """
 from __future__ import annotations
 
@@ -36,6 +41,8 @@ STATS_FIELDS = ("chunk", "chunks_total", "chunks_done", "samples_done", "kernel_
 BLOB_HEADER = 288  # RT_FRAME_BLOB_HEADER
 BLOB_VERSION = 1   # RT_FRAME_BLOB_VERSION
 BLOB_MAGIC = b"RTFRAME\0"
+CKPT_HEADER = 320  # RT_FRAME_CKPT_HEADER
+CKPT_VERSION = 2   # RT_FRAME_CKPT_VERSION
 PARAM_FIELDS = ("width", "height", "spp", "max_depth", "rng_mode", "flags", "seed", "tile", "shard_rank",
                 "shard_count")
 
@@ -132,6 +139,16 @@ class ProgressiveFrame:
         _rt._check(_rt.lib().rt_frame_save_header(self._handle(), buf, BLOB_HEADER), "rt_frame_save_header")
         return buf.raw
 
+    def checkpoint(self) -> bytes:
+        """rt_frame_checkpoint: the frame as a version-2 blob (rt.h) with its moments when it tracks them and its
+        K_p when a pixel is stopped, for `Context.resume_frame`, `Context.resume_shard_frame` and the host-only
+        `checkpoint_info` / `checkpoint_resolve` / `checkpoint_error`."""
+        n = C.c_size_t(0)
+        _rt._check(_rt.lib().rt_frame_checkpoint(self._handle(), None, 0, C.byref(n)), "rt_frame_checkpoint")
+        buf = C.create_string_buffer(n.value)
+        _rt._check(_rt.lib().rt_frame_checkpoint(self._handle(), buf, n.value, C.byref(n)), "rt_frame_checkpoint")
+        return buf.raw[:n.value]
+
     def moments(self) -> np.ndarray:
         """rt_frame_moments: Q[H,W,3], the second moments of the chunk sums (rt.h), for `restore_frame` and
         `error_estimate`. RTError (RT_E_STATE) on a frame that does not track them."""
@@ -223,6 +240,70 @@ def restore_frame(ctx, blob: bytes, moments: Optional[np.ndarray] = None) -> Pro
     return fr
 
 
+def resume_frame(ctx, blob: bytes) -> ProgressiveFrame:
+    """rt_frame_resume: the frame a version-1 or version-2 blob holds (see Context.resume_frame)."""
+    info = checkpoint_info(blob)
+    h = C.c_void_p()
+    _rt._check(_rt.lib().rt_frame_resume(ctx._h, blob, len(blob), C.byref(h)), "rt_frame_resume")
+    fr = ProgressiveFrame(ctx, h, info["params"], info["Q"] is not None)
+    fr.chunks_done, fr.active_pixels = info["chunks_done"], info["active_pixels"]
+    return fr
+
+
+def checkpoint_info(blob: bytes) -> dict:
+    """rt_frame_checkpoint_info (host only): `blob_info`'s dict of a version-1 or version-2 blob, plus `sections`,
+    the byte offsets `sums_offset` / `moments_offset` / `stops_offset`, the counts `stopped_pixels` /
+    `stopped_nan` / `active_pixels`, and read-only numpy views of the payload: `S` [H,W,3] float64, `Q` [H,W,3]
+    float64 or None, `K` [H,W] int32 (0 = active) or None. Raises RTError (RT_E_INVALID) for a malformed blob."""
+    d = _rt.rt_frame_ckpt_desc()
+    _rt._check(_rt.lib().rt_frame_checkpoint_info(blob, len(blob), C.byref(d)), "rt_frame_checkpoint_info")
+    b = d.blob
+    p = _rt.rt_render_params()
+    C.memmove(C.byref(p), C.byref(b.params), C.sizeof(p))
+    cam = _rt.rt_camera()
+    C.memmove(C.byref(cam), C.byref(b.camera), C.sizeof(cam))
+    out = {k: getattr(b, k) for k in ("version", "upload_flags", "chunk", "chunks_total", "chunks_done", "samples_done",
+                                      "pixels", "scene_fingerprint", "payload_bytes")}
+    out.update({k: getattr(p, k) for k in PARAM_FIELDS})
+    out.update({k: getattr(d, k) for k in ("sections", "sums_offset", "moments_offset", "stops_offset",
+                                           "stopped_pixels", "stopped_nan", "active_pixels")})
+    out["params"], out["camera"] = p, cam
+    H, W = p.height, p.width
+    out["S"] = np.frombuffer(blob, dtype="<f8", count=3 * W * H, offset=d.sums_offset).reshape(H, W, 3)
+    out["Q"] = (np.frombuffer(blob, dtype="<f8", count=3 * W * H, offset=d.moments_offset).reshape(H, W, 3)
+                if d.moments_offset else None)
+    out["K"] = np.frombuffer(blob, dtype="<i4", count=W * H, offset=d.stops_offset).reshape(H, W) if d.stops_offset else None
+    return out
+
+
+def checkpoint_resolve(blob: bytes, rgb: bool = True, linear: bool = True):
+    """rt_checkpoint_resolve (host only, no scene needed): (rgb8[H,W,3] | None, linear[H,W,3] | None, stats dict),
+    the preview `resolve` gives of a resumed frame; bytes_changed is taken against an all-zero image."""
+    info = checkpoint_info(blob)
+    H, W = info["height"], info["width"]
+    out_rgb = np.zeros((H, W, 3), dtype=np.uint8) if rgb else None
+    out_lin = np.zeros((H, W, 3), dtype=np.float64) if linear else None
+    s = _rt.rt_frame_stats()
+    P = C.POINTER
+    _rt._check(_rt.lib().rt_checkpoint_resolve(blob, len(blob), out_rgb.ctypes.data_as(P(C.c_uint8)) if rgb else None,
+                                               out_lin.ctypes.data_as(P(C.c_double)) if linear else None, C.byref(s)),
+               "rt_checkpoint_resolve")
+    return out_rgb, out_lin, _stats_dict(s)
+
+
+def checkpoint_error(blob: bytes, abs_tol: float = 0.0, rel_tol: float = 0.0, want_map: bool = True):
+    """rt_checkpoint_error (host only): (se[H,W,3] | None, stats dict), `ProgressiveFrame.error` of a checkpoint
+    with moments and at least two chunks, each stopped pixel at its own (K_p, N_p)."""
+    info = checkpoint_info(blob)
+    se = np.zeros((info["height"], info["width"], 3), dtype=np.float64) if want_map else None
+    tol = _rt.rt_error_tol(abs_tol, rel_tol)
+    s = _rt.rt_error_stats()
+    _rt._check(_rt.lib().rt_checkpoint_error(blob, len(blob), C.byref(tol),
+                                             se.ctypes.data_as(C.POINTER(C.c_double)) if want_map else None,
+                                             C.byref(s)), "rt_checkpoint_error")
+    return se, _error_dict(s)
+
+
 def error_estimate(sums, moments, chunks_done: int, samples_done: int, abs_tol: float = 0.0, rel_tol: float = 0.0):
     """rt_error_estimate (host only): (se, stats dict) from image-order sums (a blob's payload) and moments
     of the same shape [..., 3], by the per-pixel function `ProgressiveFrame.error` runs on the device."""
@@ -283,7 +364,8 @@ def render_progressive(ctx, cam, params, step_chunks: int,
                        stop_changed_fraction: Optional[float] = None, *,
                        stop_unconverged_fraction: Optional[float] = None, abs_tol: float = 0.0,
                        rel_tol: float = 0.0, adaptive: bool = False,
-                       min_chunks: int = 2) -> Iterator[Tuple[np.ndarray, dict]]:
+                       min_chunks: int = 2, resume: Optional[bytes] = None,
+                       checkpoint=None) -> Iterator[Tuple[np.ndarray, dict]]:
     """Yields (rgb, stats) after each step of `step_chunks` chunks. Stops at completion, or once
     bytes_changed / (3*W*H) of a step is at most `stop_changed_fraction` (the 8-bit stopping rule: the
     bytes stopped moving). `ctx` needs `open_frame(cam, params)` returning a frame with `advance`,
@@ -298,13 +380,22 @@ def render_progressive(ctx, cam, params, step_chunks: int,
     With `adaptive` the frame is opened with `moments=True` and after each step's resolve
     `frame.adapt(abs_tol, rel_tol, min_chunks)` stops the NaN pixels and the pixels converged under the
     tolerances (its stats are merged into the yielded dict; the yielded image is the one before that call,
-    which a stop does not change); the loop also ends once no pixel is active."""
+    which a stop does not change); the loop also ends once no pixel is active.
+
+    With `resume` (a blob of `ProgressiveFrame.checkpoint`, or a version-1 blob) the loop starts from
+    `ctx.resume_frame(resume)` instead of opening a frame: `cam` and `params` are then the blob's and the
+    arguments are not looked at. With `checkpoint` (a callable) every step hands it `frame.checkpoint()` after
+    the step's stop call (after the resolve when the run is not adaptive) and before the step is yielded, so a
+    run interrupted at any step continues from the last blob to the same image and stats."""
     if step_chunks < 1:
         raise ValueError("step_chunks must be at least 1")
-    channels = 3 * params.width * params.height
     by_error = stop_unconverged_fraction is not None
     tracked = by_error or adaptive
-    frame = ctx.open_frame(cam, params, moments=True) if tracked else ctx.open_frame(cam, params)
+    if resume is not None:
+        frame = ctx.resume_frame(resume)
+    else:
+        frame = ctx.open_frame(cam, params, moments=True) if tracked else ctx.open_frame(cam, params)
+    channels = 3 * params.width * params.height if resume is None else 3 * frame.width * frame.height
     try:
         while not frame.complete:
             frame.advance(step_chunks)
@@ -318,6 +409,8 @@ def render_progressive(ctx, cam, params, step_chunks: int,
                 ad = frame.adapt(abs_tol, rel_tol, min_chunks)
                 stats.update(ad)
                 met = met or ad["active_pixels"] == 0
+            if checkpoint is not None:
+                checkpoint(frame.checkpoint())
             yield rgb, stats
             if met or (stop_changed_fraction is not None and stats["bytes_changed"] <= stop_changed_fraction * channels):
                 break
@@ -404,6 +497,18 @@ class ShardFrame(ProgressiveFrame):
         _rt._check(_rt.lib().rt_frame_shard_state(self._handle(), _dev_ptr(sums), _dev_ptr(moments), _dev_ptr(chunks)),
                    "rt_frame_shard_state")
 
+    def stops_into(self, stops) -> None:
+        """rt_frame_shard_stops: the raw K_p (int32 [slab], 0 = active) in slab order into device memory."""
+        _rt._check(_rt.lib().rt_frame_shard_stops(self._handle(), _dev_ptr(stops)), "rt_frame_shard_stops")
+
+    def checkpoint_header(self, sections: int, chunks_done: int = -1) -> bytes:
+        """rt_frame_checkpoint_header: the 320 header bytes of the whole image's checkpoint; `sections` is the OR
+        over the image's shards, `chunks_done` the image's (-1: this frame's own)."""
+        buf = C.create_string_buffer(CKPT_HEADER)
+        _rt._check(_rt.lib().rt_frame_checkpoint_header(self._handle(), int(sections), int(chunks_done), buf,
+                                                        CKPT_HEADER), "rt_frame_checkpoint_header")
+        return buf.raw
+
     # ---- host conveniences (numpy slabs, staged through torch tensors on the ctx's device)
     def slab_tensor(self, dtype, channels: int = 3):
         """A zeroed torch tensor of one slab on the ctx's device: [slab_pixels, channels] (channels 0: [slab_pixels])."""
@@ -437,6 +542,13 @@ class ShardFrame(ProgressiveFrame):
         self.state_into(s, q, k)
         return s.cpu().numpy(), (q.cpu().numpy() if want_q else None), k.cpu().numpy()
 
+    def stops(self) -> np.ndarray:
+        """The raw K_p[slab] (int32, 0 = active) as a numpy slab."""
+        import torch
+        k = self.slab_tensor(torch.int32, 0)
+        self.stops_into(k)
+        return k.cpu().numpy()
+
 
 def restore_shard_frame(ctx, blob: bytes, rank: int, count: int, moments: Optional[np.ndarray] = None) -> ShardFrame:
     """rt_frame_restore_shard: shard `rank` of `count` of a whole-image blob's frame (see Context.restore_shard_frame)."""
@@ -451,10 +563,26 @@ def restore_shard_frame(ctx, blob: bytes, rank: int, count: int, moments: Option
     return fr
 
 
+def resume_shard_frame(ctx, blob: bytes, rank: int, count: int) -> ShardFrame:
+    """rt_frame_resume_shard: shard `rank` of `count` of a whole-image checkpoint's frame (see
+    Context.resume_shard_frame)."""
+    info = checkpoint_info(blob)
+    h = C.c_void_p()
+    _rt._check(_rt.lib().rt_frame_resume_shard(ctx._h, blob, len(blob), int(rank), int(count), C.byref(h)),
+               "rt_frame_resume_shard")
+    fr = ShardFrame(ctx, h, shard_params(info["params"], rank, count), info["Q"] is not None)
+    fr.chunks_done = info["chunks_done"]
+    if info["K"] is not None:
+        m = _rt.shard_pixel_map(fr.params)
+        fr.active_pixels = fr.owned_pixels - int((info["K"].reshape(-1)[m[m >= 0]] != 0).sum())
+    return fr
+
+
 class ShardedProgressiveFrame:
     """One progressive frame over `world` shard frames, with ProgressiveFrame's surface: `advance`, `resolve`
     (image, linear, merged stats), `error`, `adapt`, `stop`, `chunk_counts`, `save` (blob, moments), the
-    `restore(..., world=M)` classmethod and `close`. The result is the unsharded frame's, bit for bit.
+    `restore(..., world=M)` classmethod, `checkpoint` (the version-2 blob, adapted frames too) with the
+    `resume(..., world=M)` classmethod, and `close`. The result is the unsharded frame's, bit for bit.
 
     Local mode: `ctxs` is a list of Contexts, one per shard, in this process (the same Context may repeat; each
     needs the scene uploaded). The shards' slabs are copied to the first context's device and assembled there by
@@ -691,6 +819,51 @@ class ShardedProgressiveFrame:
         if self.rank != 0:
             return None, None
         return head + np.ascontiguousarray(sums, dtype="<f8").tobytes(), q
+
+    def checkpoint(self) -> Optional[bytes]:
+        """The whole image's version-2 checkpoint, byte for byte the unsharded frame's `checkpoint()`: the header
+        (rt_frame_checkpoint_header; sections and chunks_done reduced over the shards), the assembled sums, the
+        assembled moments of a tracked frame, and, when a pixel is stopped, the shards' raw K_p merged through
+        `shard_pixel_map`. What `resume` and `Context.resume_frame` take. None off the root."""
+        torch = self._torch()
+        stops = int(any(f.active_pixels < f.owned_pixels for f in self.frames))
+        if not self.local and self.world > 1:
+            stops = self._max_int(stops)
+        sections = (_rt.RT_CKPT_MOMENTS if self.tracks_moments else 0) | (_rt.RT_CKPT_STOPS if stops else 0)
+        head = self.frames[0].checkpoint_header(sections, self.chunks_done)
+        sums = self._state_image("sums")
+        q = self.moments() if self.tracks_moments else None
+        k = None
+        if stops:
+            ks = self._slabs_of(lambda f: f.slab_tensor(torch.int32, 0), lambda f, t: f.stops_into(t))
+            allk = self._all_slabs(ks)
+            k = self._merge_host(allk.cpu().numpy()) if self.rank == 0 else None
+        if self.rank != 0:
+            return None
+        parts = [head, np.ascontiguousarray(sums, dtype="<f8").tobytes()]
+        if q is not None:
+            parts.append(np.ascontiguousarray(q, dtype="<f8").tobytes())
+        if k is not None:
+            parts.append(np.ascontiguousarray(k, dtype="<i4").tobytes())
+        return b"".join(parts)
+
+    @classmethod
+    def resume(cls, ctxs, blob: bytes, *, world: Optional[int] = None, rank: Optional[int] = None,
+               backend: str = "nccl", gather: Optional[bool] = None):
+        """The frame a whole-image checkpoint (`checkpoint`'s, or ProgressiveFrame.checkpoint's; a version-1 blob
+        too) holds, over `world` shards, with its moments and stopped pixels: the shard count of the saved frame
+        does not matter. Local mode: world defaults to len(ctxs)."""
+        info = checkpoint_info(blob)
+        local = isinstance(ctxs, (list, tuple))
+        m = len(ctxs) if local and world is None else world
+        if m is None or (local and m != len(ctxs)):
+            raise ValueError("world must be given (local mode: one context per shard)")
+        pairs = list(zip(ctxs, range(m))) if local else [(ctxs, rank)]
+        frames = [resume_shard_frame(c, blob, r, m) for c, r in pairs]
+        fr = cls(ctxs, info["camera"], info["params"], info["Q"] is not None, rank=rank, world=m, backend=backend,
+                 gather=gather, _frames=frames)
+        fr.active_pixels = info["active_pixels"]
+        return fr
 
     def close(self):
         for f in self.frames:
