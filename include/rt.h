@@ -947,7 +947,8 @@ int rt_debug_probe(rt_ctx* ctx, const rt_camera* cam, int op, const double* in, 
  * ops: 0 x/y (IEEE), 1 div_exact(x, y) (reciprocal + Markstein), 2 sqrt x, 3 sin x, 4 cos x,
  * 5 atan x, 6 asin x, 7 log x, 8 pow(x, y), 9 GHC atan2(x, y), 10 tan x, 11 the render path's
  * x ** 5 (schlick; double-double, correctly rounded); 12-16 include/rt_libm.h's sin, cos, atan, asin,
- * log x and 17 GHC atan2(x, y) over them (RT_FLAG_SHARED_LIBM).
+ * log x and 17 GHC atan2(x, y) over them (RT_FLAG_SHARED_LIBM); 18 and 19 the sine and the cosine of x from
+ * the sincos call of the kernels that fuse the two.
  */
 int rt_debug_math(rt_ctx* ctx, int op, const double* x, const double* y, int n, double* out);
 

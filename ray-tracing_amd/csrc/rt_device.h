@@ -59,6 +59,33 @@ __device__ __forceinline__ double m_cos(double x) {
   if constexpr (SL) return rtlm_cos(x);
   else return cos(x);
 }
+// The sine and cosine of one angle. RT_FUSED_SINCOS=1 (set by a kernel unit): OCML's sincos, one range
+// reduction and one pair of polynomials for both, behind a call (sincos_call), as log and atan are (log_call,
+// sphere_uv: inlined, such a function's coefficients are held across the render loop and spilled); C2's kernel
+// 92 -> 80 B/lane of scratch, 28 -> 22 VGPR spills, -3.2 % of its time. 0: cos and then sin,
+// each with its own reduction. SL keeps rtlm_cos, then rtlm_sin.
+#ifndef RT_FUSED_SINCOS
+#define RT_FUSED_SINCOS 0
+#endif
+template <int = 0>  // (a template, so that a unit that never calls it emits no copy)
+__device__ __noinline__ double2 sincos_call(double x) {
+  double s, c;
+  sincos(x, &s, &c);
+  return make_double2(s, c);
+}
+// Where the two are fused. Elsewhere the callers keep m_cos and m_sin as they were written, so that a unit that
+// leaves RT_FUSED_SINCOS off, and every SL kernel (rtlm_cos, then rtlm_sin), compiles to the device code it had
+// before: handed to the callers as two results of one helper, the same operations reached the scheduler in
+// another order.
+template <bool SL>
+constexpr bool kFusedSincos = RT_FUSED_SINCOS && !SL;
+template <bool SL>
+__device__ __forceinline__ void m_sincos(double x, double& s, double& c) {
+  static_assert(kFusedSincos<SL>, "callers keep m_cos and m_sin where nothing fuses");
+  const double2 sc = sincos_call(x);
+  s = sc.x;
+  c = sc.y;
+}
 template <bool SL>
 __device__ __forceinline__ double m_log(double x) {
   if constexpr (SL) return rtlm_log(x);
@@ -341,7 +368,13 @@ __device__ __forceinline__ V3 random_unit_vector(R& g) {  // Lib.hs:1187-1197
   const double zz = g.draw();
   const double z = (zz * 2.0) - 1.0;
   const double r = sqrt(1.0 - z * z);
-  return v3(r * m_cos<R::kSL>(a), r * m_sin<R::kSL>(a), z);
+  if constexpr (kFusedSincos<R::kSL>) {
+    double sn, cs;
+    m_sincos<R::kSL>(a, sn, cs);
+    return v3(r * cs, r * sn, z);
+  } else {
+    return v3(r * m_cos<R::kSL>(a), r * m_sin<R::kSL>(a), z);
+  }
 }
 template <class R>
 __device__ __forceinline__ V3 random_cosine_direction(R& g) {  // Lib.hs:1206-1217
@@ -349,7 +382,13 @@ __device__ __forceinline__ V3 random_cosine_direction(R& g) {  // Lib.hs:1206-12
   const double z = sqrt(1.0 - r2);
   const double phi = 2.0 * kPi * r1;
   const double sr2 = sqrt(r2);
-  return v3(m_cos<R::kSL>(phi) * sr2, m_sin<R::kSL>(phi) * sr2, z);
+  if constexpr (kFusedSincos<R::kSL>) {
+    double sn, cs;
+    m_sincos<R::kSL>(phi, sn, cs);
+    return v3(cs * sr2, sn * sr2, z);
+  } else {
+    return v3(m_cos<R::kSL>(phi) * sr2, m_sin<R::kSL>(phi) * sr2, z);
+  }
 }
 template <class R>
 __device__ __forceinline__ V3 random_to_sphere(R& g, double radius, double dist_squared) {  // Lib.hs:1219-1228
@@ -357,7 +396,13 @@ __device__ __forceinline__ V3 random_to_sphere(R& g, double radius, double dist_
   const double z = 1.0 + r2 * (sqrt(1.0 - radius * radius / dist_squared) - 1.0);
   const double phi = 2.0 * kPi * r1;
   const double s = sqrt(1.0 - z * z);
-  return v3(m_cos<R::kSL>(phi) * s, m_sin<R::kSL>(phi) * s, z);
+  if constexpr (kFusedSincos<R::kSL>) {
+    double sn, cs;
+    m_sincos<R::kSL>(phi, sn, cs);
+    return v3(cs * s, sn * s, z);
+  } else {
+    return v3(m_cos<R::kSL>(phi) * s, m_sin<R::kSL>(phi) * s, z);
+  }
 }
 
 // ------------------------------------------------------------------ ONB (Lib.hs:263-279)

@@ -5,6 +5,9 @@
 // Philox key, as the spheres unit (rt_k_spheres.hip). The kernels live in an anonymous namespace, so each
 // unit's instantiations are its own.
 #define RT_PHILOX_OPAQUE_KEY 1
+// The shading code's fused sincos (rt_device.h): this unit only, so that every build keeps kernels on the
+// plain form (the spheres unit's, RTAMD_WIDE=0) to compare against. The other units lost with it.
+#define RT_FUSED_SINCOS 1
 #include "rt_kernels.h"
 
 namespace rt {

@@ -1348,6 +1348,16 @@ __global__ void math_probe(int op, const double* x, const double* y, int n, doub
   }
   out[i] = r;
 }
+// Ops 18 and 19: the sine and the cosine of the shading code's fused sincos (RT_FUSED_SINCOS), through the call
+// the kernels make. A kernel of its own, and a template: only the unit that launches it (rt_render.hip) emits it,
+// and the render units that leave the form off compile to the device code they had before.
+template <int = 0>
+__global__ void math_probe_sincos(int op, const double* x, int n, double* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double2 sc = sincos_call(x[i]);
+  out[i] = op == 18 ? sc.x : sc.y;
+}
 
 
 

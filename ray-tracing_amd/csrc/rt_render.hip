@@ -2155,7 +2155,7 @@ int rt_debug_probe(rt_ctx* c, const rt_camera* cam, int op, const double* in, in
 }
 
 int rt_debug_math(rt_ctx* c, int op, const double* x, const double* y, int n, double* out) {
-  if (!c || !x || !y || !out || n < 0 || op < 0 || op > 17) return invalid("rt_debug_math: bad argument");
+  if (!c || !x || !y || !out || n < 0 || op < 0 || op > 19) return invalid("rt_debug_math: bad argument");
   if (n == 0) return RT_OK;
   DEVICE_SCOPE(c->device);
   const size_t bytes = sizeof(double) * (size_t)n;
@@ -2166,7 +2166,8 @@ int rt_debug_math(rt_ctx* c, int op, const double* x, const double* y, int n, do
   double *dx = (double*)bx.p, *dy = (double*)by.p, *dout = (double*)bout.p;
   HIPCHK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(math_probe, dim3((n + 255) / 256), dim3(256), 0, c->stream, op, dx, dy, n, dout);
+  if (op >= 18) hipLaunchKernelGGL(math_probe_sincos<0>, dim3((n + 255) / 256), dim3(256), 0, c->stream, op, dx, n, dout);
+  else hipLaunchKernelGGL(math_probe, dim3((n + 255) / 256), dim3(256), 0, c->stream, op, dx, dy, n, dout);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));

@@ -1839,7 +1839,9 @@ __device__ __forceinline__ void scatter(const Scene& S, const DMat& m, const Ray
   if (metal || (lamb && !light)) {
     const double a = g.draw(), b = g.draw();
     const double ang = 2.0 * kPi * a;
-    const double cs = m_cos<R::kSL>(ang), sn = m_sin<R::kSL>(ang);
+    double sn, cs;
+    if constexpr (kFusedSincos<R::kSL>) m_sincos<R::kSL>(ang, sn, cs);
+    else cs = m_cos<R::kSL>(ang), sn = m_sin<R::kSL>(ang);
     const double z = (b * 2.0) - 1.0;                      // Metal: z = 2 zz - 1
     const double q = sqrt(metal ? 1.0 - z * z : 1.0 - b);  // Metal: r; Lambertian: z
     const double sr2 = sqrt(b);

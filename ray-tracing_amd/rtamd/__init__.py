@@ -46,7 +46,8 @@ RT_BVH_ORDERED = 0x40000000
 RT_BVH_MEDIA_FIRST = 0x10000000
 MATH_OPS = {"div": 0, "div_exact": 1, "sqrt": 2, "sin": 3, "cos": 4, "atan": 5, "asin": 6, "log": 7, "pow": 8,
             "ghc_atan2": 9, "tan": 10, "pow5": 11, "sl_sin": 12, "sl_cos": 13, "sl_atan": 14, "sl_asin": 15,
-            "sl_log": 16, "sl_ghc_atan2": 17}  # sl_*: include/rt_libm.h (RT_FLAG_SHARED_LIBM)
+            "sl_log": 16, "sl_ghc_atan2": 17,  # sl_*: include/rt_libm.h (RT_FLAG_SHARED_LIBM)
+            "sincos_sin": 18, "sincos_cos": 19}  # the two halves of the packed spheres unit's sincos call
 
 # rt_debug_probe / oracle_probe: function -> op id, doubles per input / output record (rt.h)
 PROBES = {"scatter": 0, "htbl_random": 1, "htbl_pdf": 2, "texture": 3, "get_ray": 4, "box": 5}
