@@ -66,6 +66,18 @@ inline int bvh_stack_need(const rt_node& x, int need_a, int need_b) {
 extern "C" int rt_internal_work_units(const rt_render_params* p, int chunk_first, int n_chunks, long long tail_items,
                                       uint32_t first, int n, int32_t* out5, int64_t* out_slot, int64_t* out_totals);
 
+// The plan of a tier-B launch (rt_launch_plan.h), decided without a device: `desc` prepared as an upload with
+// `upload_flags` prepares it, on a device of `cu_count` CUs, for `span_count` chunks from `span_first` (-1: the
+// whole frame) of the frame `p` describes, as the counting build (`count_build`) or an adaptive frame's launch
+// (`adaptive`), under the environment's RTAMD_* knobs. *out = what rt_last_launch would report, with the blocks
+// the work asks for as `grid` where the launcher bounds it by residency (no LDS staging). out_extra (may be
+// null) = {n_items, entries, n_leaves, trav_stop, leaf_stop, box_first, med_batch, batch, batch_floor,
+// rev_tiles, tail_items, chunks per launch, wide_packed, KernelUnit, grid, the form's WAVES}.
+#define RT_PLAN_EXTRA 16
+extern "C" int rt_internal_launch_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count,
+                                       const rt_render_params* p, int span_first, int span_count, int count_build,
+                                       int adaptive, rt_launch_info* out, int32_t* out_extra);
+
 struct rt_builder {
   uint64_t seed, gamma;  // RandGen (SMGen)
   std::vector<rt_node> nodes;

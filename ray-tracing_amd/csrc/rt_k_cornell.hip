@@ -5,7 +5,5 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip, bool pk) {
-  return pick<kVarCornell>(loop, lds, w, count, leaf_lds, false, skip, pk);
-}
+const void* philox_kernel_cornell(const KernelForm& f) { return pick<kVarCornell>(f); }
 }  // namespace rt

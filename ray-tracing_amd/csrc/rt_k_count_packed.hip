@@ -6,8 +6,8 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_count_packed(unsigned var) {
-  if (var == kVarSpheres) return (const void*)render_philox2_count_packed<kVarSpheres | F_WIDE | F_COUNT>;
+const void* philox_kernel_count_packed(const KernelForm& f) {
+  if (f.var == kVarSpheres) return (const void*)render_philox2_count_packed<kVarSpheres | F_WIDE | F_COUNT>;
   return (const void*)render_philox2_count_packed<kVarCornell | F_WIDE | F_COUNT>;
 }
 }  // namespace rt

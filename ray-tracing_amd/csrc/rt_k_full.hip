@@ -4,7 +4,5 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_full(int loop, bool lds, int w, bool count, bool skip) {
-  return pick_full<kVarFull>(loop, lds, w, count, skip);
-}
+const void* philox_kernel_full(const KernelForm& f) { return pick_full<kVarFull>(f); }
 }  // namespace rt

@@ -5,7 +5,5 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count, bool skip) {
-  return pick_full<kVarFullDark>(loop, lds, w, count, skip);
-}
+const void* philox_kernel_full_dark(const KernelForm& f) { return pick_full<kVarFullDark>(f); }
 }  // namespace rt

@@ -7,8 +7,5 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q, bool skip, bool pk) {
-  if (loop == 2 && lds && pk && !count) return philox_kernel_spheres_packed(w, leaf_lds, skip);
-  return pick<kVarSpheres>(loop, lds, w, count, leaf_lds, q, skip);
-}
+const void* philox_kernel_spheres(const KernelForm& f) { return pick<kVarSpheres>(f); }
 }  // namespace rt

@@ -7,12 +7,9 @@
 namespace rt {
 template <unsigned V>
 const void* global_kernel(int w) {
-  if (w == 2) return (const void*)render_philox2<V, 2>;
-  if (w == 4) return (const void*)render_philox2<V, 4>;
-  if (w == 1) return (const void*)render_philox2<V, 1>;
-  return (const void*)render_philox2<V, 3>;
+  return by_waves<1, 2, 3, 4>(w, [](auto W) { return (const void*)render_philox2<V, W()>; });
 }
-const void* philox_kernel_spheres_global(int w, bool skip) {
-  return skip ? global_kernel<kVarSpheres | F_WIDE | F_SKIP>(w) : global_kernel<kVarSpheres | F_WIDE>(w);
+const void* philox_kernel_spheres_global(const KernelForm& f) {
+  return f.skip ? global_kernel<kVarSpheres | F_WIDE | F_SKIP>(f.waves) : global_kernel<kVarSpheres | F_WIDE>(f.waves);
 }
 }  // namespace rt

@@ -11,7 +11,7 @@
 #include "rt_kernels.h"
 
 namespace rt {
-const void* philox_kernel_spheres_packed(int w, bool leaf_lds, bool skip) {
-  return skip ? pick_packed<kVarSpheres | F_WIDE | F_SKIP>(w, leaf_lds) : pick_packed<kVarSpheres | F_WIDE>(w, leaf_lds);
+const void* philox_kernel_spheres_packed(const KernelForm& f) {
+  return f.skip ? pick_packed<kVarSpheres | F_WIDE | F_SKIP>(f) : pick_packed<kVarSpheres | F_WIDE>(f);
 }
 }  // namespace rt

@@ -11,12 +11,14 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rt.h"
 #include "rt_device.h"
 #include "rt_error.h"
 #include "rt_internal.h"
+#include "rt_launch_plan.h"
 #include "rt_trace.h"
 
 using namespace rtd;
@@ -134,7 +136,7 @@ __global__ void __launch_bounds__(64) launch_setup(LaunchConst L, LaunchConst* d
 }
 
 // Slab pixel index -> image pixel (tile-major, 8x8 blocks inside a tile). Slab indices are < 2^32
-// (launch_philox checks).
+// (plan_launch checks).
 __host__ __device__ __forceinline__ bool work_pixel(const LaunchConst& A, uint32_t w, int& px, int& row) {
   const uint32_t tp = (uint32_t)(A.tile * A.tile);
   const uint32_t lt = udiv(w, A.div_tp);
@@ -446,7 +448,6 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES) render_philox_lds(RenderAr
   philox_loop<F>(A, L, S, stk, WAVES * 256);
 }
 
-
 // Tier-B loop with ray replacement (media-free worlds without instance frames): traversal state
 // persists in registers across iterations; each iteration first shades the lanes whose walk has
 // ended and starts their next segment (or sample, or pixel), then steps every walking lane one
@@ -464,7 +465,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
   bool done = false, walking = false, ready = false;
   // wq[0..1]: the wave's claimed, not yet handed out work-items [next, end), in LDS (lanes that
   // are walking skip the acquisition code, so a per-lane copy would go stale); indices are < 2^32
-  // (launch_philox checks)
+  // (plan_launch checks)
   if (lane == 0) {
     wq[0] = 0u;
     wq[1] = 0u;
@@ -715,7 +716,7 @@ __global__ void __launch_bounds__(RT_BLOCK, WAVES) render_philox2(RenderArgs A, 
                   wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
 }
 
-// The counting build of a 4-wide world whose timed launch takes the packed form (launch_philox): the same
+// The counting build of a 4-wide world whose timed launch takes the packed form (plan_launch): the same
 // global-memory loop with wide_node<F, true> and the stack cull, so that the work counters describe the walk the
 // timed kernel does. A kernel of its own (rt_k_count_packed.hip), so that no timed kernel's name or unit changes.
 template <unsigned F>
@@ -770,7 +771,7 @@ __global__ void __launch_bounds__(WAVES * 256, WAVES)
   unsigned char* lane_base = lds + (size_t)n_nodes * rec + (size_t)n_leaves * lrec;
   int* stk = reinterpret_cast<int*>(lane_base) + threadIdx.x;
   // (per lane: stack_entries stack entries, then side_ints_of Side slots, then lane_lds_of's 4 lane ints —
-  // launch_philox sizes the dynamic LDS with the same helpers)
+  // plan_launch sizes the dynamic LDS with the same helpers)
   int* side_p = reinterpret_cast<int*>(lane_base + (size_t)stack_entries * lanes * sizeof(int)) + threadIdx.x;
   philox_loop2<F, PK>(A, L, S, stk, lanes, side_p, wave_q[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
 }
@@ -1359,110 +1360,86 @@ __global__ void math_probe_sincos(int op, const double* x, int n, double* out) {
   out[i] = op == 18 ? sc.x : sc.y;
 }
 
-
-
-// Kernel pointer for (variant, loop, LDS-staged?, waves per SIMD, counting build?); loop 0 = one
-// sample per lane walk, 1 = ray replacement over the binary tree, 2 = replacement over the
-// 4-wide tree. `skip`: the F_SKIP instantiation of the same kernel (an adaptive frame's launches; there
-// is no counting build of those).
-// The LDS-staged 4-wide kernels that sort packed keys (worlds within rt_wkey_fits: launch_philox).
+// The kernel instantiation of a KernelForm (rt_launch_plan.h; plan_launch makes only forms that exist).
+// `V` carries the variant with F_WIDE and F_SKIP; the F_SKIP instantiations are the same kernels for an
+// adaptive frame's launches (there is no counting build of those).
+// by_waves<Ws...>(w, k): k(std::integral_constant<int, w>) for the w among Ws, the WAVES values the kernel
+// is instantiated with; nullptr for any other.
+template <int... Ws, class K>
+const void* by_waves(int w, K k) {
+  const void* fn = nullptr;
+  (void)((w == Ws && (fn = k(std::integral_constant<int, Ws>{}), true)) || ...);
+  return fn;
+}
+// The LDS-staged 4-wide kernels that sort packed keys (worlds within rt_wkey_fits: wide_keys_packed).
 template <unsigned V>
-const void* pick_packed(int w, bool leaf_lds) {
+const void* pick_packed(const rt::KernelForm& f) {
   static_assert((V & F_WIDE) != 0, "4-wide kernels only");
-  if (leaf_lds) {
-    if (w == 4) return (const void*)render_philox2_lds<V, 4, true, true>;
-    if (w == 2) return (const void*)render_philox2_lds<V, 2, true, true>;
-    if (w == 3) return (const void*)render_philox2_lds<V, 3, true, true>;
-  }  // (1 wave: the leaves are read from global memory)
-  if (w == 2) return (const void*)render_philox2_lds<V, 2, false, true>;
-  if (w == 4) return (const void*)render_philox2_lds<V, 4, false, true>;
-  if (w == 1) return (const void*)render_philox2_lds<V, 1, false, true>;
-  return (const void*)render_philox2_lds<V, 3, false, true>;
+  // (1 wave: the leaves are read from global memory)
+  if (f.leaf_lds)
+    return by_waves<2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox2_lds<V, W(), true, true>; });
+  return by_waves<1, 2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox2_lds<V, W(), false, true>; });
 }
 template <unsigned V>
-const void* pick_w(bool lds, int w, bool leaf_lds = false, bool q = false, bool pk = false) {
+const void* pick_w(const rt::KernelForm& f) {
   if constexpr ((V & ~F_SKIP) == (kVarSpheres | F_WIDE)) {
-    if (!lds && q) {  // (the quantised tree and sphere quadruples from global memory)
-      if (w == 2) return (const void*)render_philox2<V | F_QNODE, 2>;
-      if (w == 3) return (const void*)render_philox2<V | F_QNODE, 3>;
-      if (w == 4) return (const void*)render_philox2<V | F_QNODE, 4>;
-      return (const void*)render_philox2<V | F_QNODE, 1>;
-    }
+    if (!f.lds && f.q)  // (the quantised tree and sphere quadruples from global memory)
+      return by_waves<1, 2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox2<V | F_QNODE, W()>; });
   }
   // (the spheres-only variant's packed kernels are instantiated in a unit of their own, rt_k_spheres_packed.hip)
   if constexpr ((V & F_WIDE) != 0 && (V & ~F_SKIP) != (kVarSpheres | F_WIDE)) {
-    if (lds && pk) return pick_packed<V>(w, leaf_lds);
+    if (f.lds && f.pk) return pick_packed<V>(f);
   }
   if constexpr ((V & F_WIDE) != 0) {
-    if (lds && leaf_lds) {
-      if (w == 4) return (const void*)render_philox2_lds<V, 4, true>;
-      if (w == 2) return (const void*)render_philox2_lds<V, 2, true>;
-      if (w == 3) return (const void*)render_philox2_lds<V, 3, true>;
-    }  // (1 wave: the leaves are read from global memory)
+    if (f.lds && f.leaf_lds)
+      return by_waves<2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox2_lds<V, W(), true>; });
   }
-  if (lds) {
-    if (w == 2) return (const void*)render_philox2_lds<V, 2>;
-    if (w == 4) return (const void*)render_philox2_lds<V, 4>;
-    if (w == 1) return (const void*)render_philox2_lds<V, 1>;
-    return (const void*)render_philox2_lds<V, 3>;
-  }
-  if (w == 2) return (const void*)render_philox2<V, 2>;
-  if (w == 3) return (const void*)render_philox2<V, 3>;
-  if (w == 4) return (const void*)render_philox2<V, 4>;
-  return (const void*)render_philox2<V, 1>;
+  if (f.lds) return by_waves<1, 2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox2_lds<V, W()>; });
+  return by_waves<1, 2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox2<V, W()>; });
 }
 template <unsigned V>
-const void* pick(int loop, bool lds, int w, bool count, bool leaf_lds, bool q = false, bool skip = false,
-                 bool pk = false) {
+const void* pick(const rt::KernelForm& f) {
   if constexpr ((V & F_SKIP) == 0) {
-    if (skip) return count ? nullptr : pick<V | F_SKIP>(loop, lds, w, false, leaf_lds, q, false, pk);
-    if (count) {
+    if (f.skip) return f.count ? nullptr : pick<V | F_SKIP>(f);
+    if (f.count) {
       if constexpr (V == kVarSpheres) {
-        if (loop == 2 && q) return (const void*)render_philox2<V | F_WIDE | F_COUNT | F_QNODE, 1>;
+        if (f.loop == 2 && f.q) return (const void*)render_philox2<V | F_WIDE | F_COUNT | F_QNODE, 1>;
       }
-      if (loop == 2) return (const void*)render_philox2<V | F_WIDE | F_COUNT, 1>;
-      return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
+      if (f.loop == 2) return (const void*)render_philox2<V | F_WIDE | F_COUNT, 1>;
+      return f.loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
     }
   }
-  if (loop == 2) return pick_w<V | F_WIDE>(lds, w, leaf_lds, q, pk);
-  if (loop == 1) return pick_w<V>(lds, w);
-  if (lds) {
-    if (w == 2) return (const void*)render_philox_lds<V, 2>;
-    if (w == 4) return (const void*)render_philox_lds<V, 4>;
-    if (w == 1) return (const void*)render_philox_lds<V, 1>;
-    return (const void*)render_philox_lds<V, 3>;
-  }
-  if (w == 2) return (const void*)render_philox<V, 2>;
-  if (w == 3) return (const void*)render_philox<V, 3>;
-  if (w == 4) return (const void*)render_philox<V, 4>;
-  return (const void*)render_philox<V, 1>;
+  if (f.loop == 2) return pick_w<V | F_WIDE>(f);
+  if (f.loop == 1) return pick_w<V>(f);
+  if (f.lds) return by_waves<1, 2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox_lds<V, W()>; });
+  return by_waves<1, 2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox<V, W()>; });
 }
 // full variants (media, frames, textures, motion): ray replacement over the caller's tree in the
 // reference's order (loop 1), or the per-sample loop (loop 0)
 template <unsigned V>
-const void* pick_full(int loop, bool lds, int w, bool count, bool skip = false) {
+const void* pick_full(const rt::KernelForm& f) {
   if constexpr ((V & F_SKIP) == 0) {
-    if (skip) return count ? nullptr : pick_full<V | F_SKIP>(loop, lds, w, false);
-    if (count) return loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
+    if (f.skip) return f.count ? nullptr : pick_full<V | F_SKIP>(f);
+    if (f.count)
+      return f.loop ? (const void*)render_philox2<V | F_COUNT, 1> : (const void*)render_philox<V | F_COUNT, 1>;
   }
-  if (loop) {
-    if (lds) return w >= 3 ? (const void*)render_philox2_lds<V, 3> : (const void*)render_philox2_lds<V, 2>;
-    if (w >= 4) return (const void*)render_philox2<V, 4>;  // (RTAMD_WAVES=4: A/B only)
-    return w >= 3 ? (const void*)render_philox2<V, 3> : (const void*)render_philox2<V, 2>;
+  if (f.loop) {
+    if (f.lds) return by_waves<2, 3>(f.waves, [](auto W) { return (const void*)render_philox2_lds<V, W()>; });
+    // (4: RTAMD_WAVES=4, A/B only)
+    return by_waves<2, 3, 4>(f.waves, [](auto W) { return (const void*)render_philox2<V, W()>; });
   }
-  return w >= 2 ? (const void*)render_philox<V, 2> : (const void*)render_philox<V, 1>;
+  return by_waves<1, 2>(f.waves, [](auto W) { return (const void*)render_philox<V, W()>; });
 }
 
 }  // namespace
 
-// Render-kernel tables, one per kernel translation unit: the kernel for (loop, LDS-staged?, waves per
-// SIMD, counting build?, leaf table in LDS?) of that unit's variant(s).
+// Render-kernel tables, one per kernel translation unit (KernelForm::unit and, for kUnitVariant, ::var).
 namespace rt {
-const void* philox_kernel_spheres(int loop, bool lds, int w, bool count, bool leaf_lds, bool q, bool skip, bool pk);
-const void* philox_kernel_spheres_global(int w, bool skip);  // rt_k_spheres_global.hip
-const void* philox_kernel_spheres_packed(int w, bool leaf_lds, bool skip);  // rt_k_spheres_packed.hip
-const void* philox_kernel_count_packed(unsigned var);  // rt_k_count_packed.hip (kVarSpheres or kVarCornell)
-const void* philox_kernel_cornell(int loop, bool lds, int w, bool count, bool leaf_lds, bool skip, bool pk);
-const void* philox_kernel_full(int loop, bool lds, int w, bool count, bool skip);
-const void* philox_kernel_full_dark(int loop, bool lds, int w, bool count, bool skip);
+const void* philox_kernel_spheres(const KernelForm& f);
+const void* philox_kernel_spheres_global(const KernelForm& f);  // rt_k_spheres_global.hip
+const void* philox_kernel_spheres_packed(const KernelForm& f);  // rt_k_spheres_packed.hip
+const void* philox_kernel_count_packed(const KernelForm& f);    // rt_k_count_packed.hip (kVarSpheres or kVarCornell)
+const void* philox_kernel_cornell(const KernelForm& f);
+const void* philox_kernel_full(const KernelForm& f);
+const void* philox_kernel_full_dark(const KernelForm& f);
 }  // namespace rt

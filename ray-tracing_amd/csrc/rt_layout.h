@@ -87,6 +87,57 @@ inline unsigned variant_for(unsigned f) {
 }
 inline bool is_full(unsigned var) { return (var & F_FRAMES) != 0; }
 
+// Side ints per lane for frames nesting `frames` deep: the world ray (14), then the open frames and the
+// frames around the best hit. The host sizes the dynamic LDS per scene: C4's two-deep frames take 8 ints
+// per lane fewer than RT_MAX_FRAMES would. (The world ray's reciprocals stored as well, 6 more ints, would
+// spare prep's divisions when the last frame closes, but take C4's kernel past six blocks per CU: 243.8
+// -> 250.1 ms at 100 spp.)
+constexpr int side_ints_for(int frames) { return 14 + 2 * frames; }
+// The replacement loop's per-lane LDS ints after the walk stack (philox_loop2's layout, plan_launch's
+// sizing — one definition for both): Side slots for the frame kernels on the binary / mixed walk (loop
+// 1), then, with RT_LANE_LDS, the 4 lane ints (pixel, row, chunk end, depth) of the
+// reference-order kernels (RT_LANE_LDS 1) or of every replacement-loop kernel (2).
+#ifndef RT_LANE_LDS
+#define RT_LANE_LDS 1
+#endif
+constexpr int side_ints_of(unsigned var, int frames, int loop) {
+  return ((var & F_FRAMES) && loop == 1) ? side_ints_for(frames) : 0;
+}
+constexpr bool lane_lds_of(unsigned var, int loop) {
+  return loop >= 1 && (RT_LANE_LDS >= 2 || (RT_LANE_LDS == 1 && (var & (F_MEDIA | F_FRAMES)) != 0));
+}
+
+// Tile edge when the caller leaves it 0 (round 5: 8, was 16; work order and shard dealing only, the
+// image does not depend on it: C2 136.0-136.2 -> 135.5 ms, its 8-shard probe 19.1 -> 18.9 ms slowest
+// shard, C3 320.0 -> 318.7, C4 at 100 spp 153.3 -> 148.6, C5 at 64 spp 653.0 -> 651.8)
+constexpr int kDefaultTile = 8;
+// The work geometry of a tier-B frame: its tiles, its shard's slab, its sample chunks (`chunk_knob`:
+// LaunchKnobs::chunk, 0 = rt.h's rt_sample_chunk) ...
+struct FrameGeometry {
+  int tile, tiles_x;
+  long long tiles_total, per_shard, slab;
+  int chunk, chunks;
+};
+inline FrameGeometry frame_geometry(const rt_render_params* p, int chunk_knob = 0) {
+  FrameGeometry g{};
+  g.tile = p->tile ? p->tile : kDefaultTile;
+  const int shards = p->shard_count > 0 ? p->shard_count : 1;
+  g.tiles_x = (p->width + g.tile - 1) / g.tile;
+  const int tiles_y = (p->height + g.tile - 1) / g.tile;
+  g.tiles_total = (long long)g.tiles_x * tiles_y;
+  g.per_shard = (g.tiles_total + shards - 1) / shards;
+  g.slab = g.per_shard * g.tile * g.tile;
+  g.chunk = rt_sample_chunk((int64_t)p->width * p->height, p->spp);
+  if (chunk_knob > 0) g.chunk = chunk_knob < p->spp ? chunk_knob : p->spp;
+  g.chunks = (p->spp + g.chunk - 1) / g.chunk;
+  return g;
+}
+// ... and the claimable units of one launch over `items` work-items whose last `tail_items` are dealt one
+// sample per unit.
+inline long long launch_units(long long items, long long tail_items, int chunk) {
+  return items + (items < tail_items ? items : tail_items) * (chunk - 1);
+}
+
 // Device material: the rt_material record plus whether its texture tree reads (u, v).
 struct DMat {
   int type;

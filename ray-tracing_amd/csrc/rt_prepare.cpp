@@ -5,6 +5,8 @@
 // rt_scene.cpp, rt_scenes.cpp) under AddressSanitizer + UBSan for the malformed-descriptor tests.
 #include "rt_prepare.h"
 
+#include "rt_launch_plan.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -449,6 +451,32 @@ int prepare_scene(const rt_scene_desc* din, uint32_t flags, PreparedScene& P) {
   if (P.replace_ok && P.ref_walk && !env_off("RTAMD_MIXW"))
     mixed_wide_trees(P, nodes, untagged, d->world_root, v.stack_need[unfolded]);
   return RT_OK;
+}
+
+// What the tier-B launch decision reads of the prepared world (rt_launch_plan.h).
+WorldShape world_shape(const PreparedScene& P, int cu_count) {
+  WorldShape W;
+  W.features = P.features;
+  W.n_nodes = (int)P.nodes.size();
+  W.n_wnodes = (int)P.wnodes.size();
+  W.n_leaves = (int)P.leaves.size();
+  W.stack_need = P.stack_need;
+  W.wide_stack_need = P.wide_stack_need;
+  W.frames = std::max(1, std::min(RT_MAX_FRAMES, P.frame_depth));
+  W.has_wide = !P.wnodes.empty();
+  W.has_qnodes = !P.qnodes.empty();
+  W.rebuilt_bvh = P.rebuilt_bvh;
+  W.mixed_wide = P.mixed_wide;
+  W.replace_ok = P.replace_ok;
+  // The division-free box test (rt_trace.h box_hit) reads an infinite slab product as the quotient; with
+  // |origin| <= 2^100 (ray_safe) and |d| >= 2^-900 that holds while every finite box coordinate is within
+  // 2^100 (no finite quotient overflows as a product). Worlds beyond it are walked with the reference's
+  // per-axis test alone (RT_FLAG_REFERENCE_CULL), which divides.
+  for (const rt_node& x : P.nodes)
+    if ((x.type & RT_TYPE_MASK) == RT_NODE_BVH)
+      for (int k = 0; k < 6; ++k) W.far_boxes |= std::isfinite(x.f[k]) && std::fabs(x.f[k]) > 0x1p100;
+  W.cu_count = cu_count;
+  return W;
 }
 
 }  // namespace rt

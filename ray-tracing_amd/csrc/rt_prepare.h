@@ -33,4 +33,8 @@ struct PreparedScene {
 // Validates `desc` and prepares its device copy (RT_OK, or an error code with rt_last_error set).
 int prepare_scene(const rt_scene_desc* desc, uint32_t flags, PreparedScene& out);
 
+// What the tier-B launch decision reads of a prepared world, for a device of `cu_count` CUs (rt_launch_plan.h).
+struct WorldShape;
+WorldShape world_shape(const PreparedScene& P, int cu_count);
+
 }  // namespace rt

@@ -32,12 +32,10 @@
 #include "rt_kernels.h"
 #include "rt_prepare.h"
 
-
 // =================================================================== host side
 struct rt_ctx {
   int device = 0;
   int cu_count = 0;
-  int blocks_per_cu = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // Recorded after every tier-B launch: the next launch (on any stream) waits on it before it
@@ -52,29 +50,14 @@ struct rt_ctx {
   rt_image* d_images = nullptr;
   uint8_t* d_pool = nullptr;
   Scene scene{};
-  unsigned features = 0;
-  int n_nodes = 0;
+  rt::WorldShape shape;  // the uploaded world's counts and kinds (what the launch decision reads)
   int n_materials = 0, n_textures = 0;  // (rt_debug_probe checks record ids against them)
-  int stack_need = 0;  // deepest traversal stack the world tree needs (entries)
   rt_wnode* d_wnodes = nullptr;  // 4-wide world tree (replace_ok worlds with a BVH root)
   rt_node* d_leaves = nullptr;   // its leaf table (Scene::leaves)
   rt_qnode* d_qnodes = nullptr;  // spheres-only worlds: the 4-wide tree quantised (Scene::qnodes)
   double* d_sleaves = nullptr;   // and the leaf table's spheres (Scene::sleaves)
-  int n_leaves = 0;
-  int n_wnodes = 0;
-  int wide_stack_need = 0;
-  bool rebuilt_bvh = false;
-  bool far_boxes = false;    // a BVH box coordinate beyond 2^100: the walks take the per-axis box test (cull())
-  bool mixed_wide = false;   // media / frame world with 4-wide trees over its re-bounded subtrees (F_MIXW)
-  bool replace_ok = false;  // frames nest <= RT_MAX_FRAMES deep: the replacement loop applies
   bool has_scene = false;
   unsigned long long* d_counter = nullptr;
-  double* d_partial = nullptr;  // tier-B chunk sums (grown on demand, at most kPartialCap)
-  size_t partial_bytes = 0;
-  double* d_tail = nullptr;     // tier-B tail units' sample colours (LaunchConst::tail_buf), grown on demand
-  size_t tail_bytes = 0;
-  double* d_acc = nullptr;      // running per-pixel sums of a frame rendered in chunk batches
-  size_t acc_bytes = 0;
   double last_ms = 0.0;
   rt_launch_info last_launch{};  // rt_last_launch
   int last_wide_packed = 0;      // the last 4-wide walk sorted packed keys (rt_debug_wide_keys)
@@ -94,6 +77,9 @@ struct rt_ctx {
     size_t bytes = 0;
   };
   FrameBuf fb_slab, fb_slab_lin, fb_gather, fb_gather_lin, fb_img, fb_img_lin, fb_gens;
+  // tier-B scratch, grown on demand: a launch's chunk sums (at most rt::kPartialCap), its tail units' sample
+  // colours (LaunchConst::tail_buf), the running per-pixel sums of a frame rendered in chunk batches
+  FrameBuf fb_partial, fb_tail, fb_acc;
   int allocs = 0;  // hipMalloc calls made on this device by the current rt_render (rt_frame_timing)
   // Progressive frames open on this ctx (rt_frame_*), and what a saved frame records of the scene: the
   // fingerprint of the caller's descriptor and the upload flags (rt_frame_blob.cpp)
@@ -145,13 +131,13 @@ struct rt_frame {
   size_t used = 0;
 };
 
-// The chunks one launch_philox call renders. Default: the whole frame, folded through the ctx's d_acc
+// The chunks one launch_philox call renders. Default: the whole frame, folded through the ctx's fb_acc
 // into the stored image. A progressive frame renders `count` chunks from `first` and keeps the running
 // sums in its own buffer.
 struct ChunkSpan {
   int first = 0;
   int count = -1;           // -1: every chunk of the frame
-  double* acc = nullptr;    // running sums between launches; nullptr: the ctx's d_acc, grown on demand
+  double* acc = nullptr;    // running sums between launches; nullptr: the ctx's fb_acc, grown on demand
   bool keep = false;        // keep the running sums in `acc` after the last chunk (no image is stored)
   double* moments = nullptr;  // a tracked frame's second moments, folded with the sums (combine_chunks_moments)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;  // around the render launches; nullptr: the ctx's ev0 / ev1
@@ -225,7 +211,7 @@ int grow(rt_ctx* c, rt_ctx::FrameBuf& b, size_t need) {
 }
 void free_frame_bufs(rt_ctx* c) {
   for (rt_ctx::FrameBuf* b : {&c->fb_slab, &c->fb_slab_lin, &c->fb_gather, &c->fb_gather_lin, &c->fb_img,
-                              &c->fb_img_lin, &c->fb_gens}) {
+                              &c->fb_img_lin, &c->fb_gens, &c->fb_partial, &c->fb_tail, &c->fb_acc}) {
     (void)hipFree(b->p);
     b->p = nullptr;
     b->bytes = 0;
@@ -242,29 +228,13 @@ int unsupported(const std::string& s) {
 }
 
 void free_scene(rt_ctx* c) {
-  (void)hipFree(c->d_nodes);
-  (void)hipFree(c->d_mats);
-  (void)hipFree(c->d_texs);
-  (void)hipFree(c->d_perlins);
-  (void)hipFree(c->d_images);
-  (void)hipFree(c->d_pool);
-  (void)hipFree(c->d_wnodes);
-  (void)hipFree(c->d_leaves);
-  (void)hipFree(c->d_qnodes);
-  (void)hipFree(c->d_sleaves);
-  c->d_wnodes = nullptr;
-  c->d_leaves = nullptr;
-  c->d_qnodes = nullptr;
-  c->d_sleaves = nullptr;
-  c->mixed_wide = false;
-  c->n_leaves = 0;
-  c->n_wnodes = 0;
-  c->d_nodes = nullptr;
-  c->d_mats = nullptr;
-  c->d_texs = nullptr;
-  c->d_perlins = nullptr;
-  c->d_images = nullptr;
-  c->d_pool = nullptr;
+  for (void** p : {(void**)&c->d_nodes, (void**)&c->d_mats, (void**)&c->d_texs, (void**)&c->d_perlins,
+                   (void**)&c->d_images, (void**)&c->d_pool, (void**)&c->d_wnodes, (void**)&c->d_leaves,
+                   (void**)&c->d_qnodes, (void**)&c->d_sleaves}) {
+    (void)hipFree(*p);
+    *p = nullptr;
+  }
+  c->shape = rt::WorldShape{};
   c->has_scene = false;
 }
 
@@ -276,10 +246,6 @@ int upload(T** dst, const T* src, size_t count) {
   return RT_OK;
 }
 
-// Tile edge when the caller leaves it 0 (round 5: 8, was 16; work order and shard dealing only, the
-// image does not depend on it: C2 136.0-136.2 -> 135.5 ms, its 8-shard probe 19.1 -> 18.9 ms slowest
-// shard, C3 320.0 -> 318.7, C4 at 100 spp 153.3 -> 148.6, C5 at 64 spp 653.0 -> 651.8)
-constexpr int kDefaultTile = 8;
 int check_params(const rt_render_params* p) {
   if (!p) return invalid("null params");
   if (p->width <= 0 || p->height <= 0 || p->spp <= 0 || p->max_depth < 0)
@@ -296,63 +262,25 @@ int check_params(const rt_render_params* p) {
   return RT_OK;
 }
 
-void geometry(const rt_render_params* p, int& tile, int& tiles_x, long long& tiles_total, long long& per_shard,
-              long long& slab_pixels) {
-  tile = p->tile ? p->tile : kDefaultTile;
-  const int shards = p->shard_count > 0 ? p->shard_count : 1;
-  tiles_x = (p->width + tile - 1) / tile;
-  const int tiles_y = (p->height + tile - 1) / tile;
-  tiles_total = (long long)tiles_x * tiles_y;
-  per_shard = (tiles_total + shards - 1) / shards;
-  slab_pixels = per_shard * tile * tile;
-}
-
-// Most bytes of chunk sums one launch writes (2 GiB; C5 at 2000 spp: 24.9 GB of chunk sums in 13 batches)
-constexpr size_t kPartialCap = 2ull << 30;
-
-// Dynamic LDS a CU's workgroup may take: 160 KiB less the replacement loop's static per-wave work
-// queues (16 waves x 8 B).
-constexpr size_t kLdsBudget = 160 * 1024 - 16 * 8;
 // The ctx's work-counter allocation: the counter's 256 bytes, then the device copy of the launch
 // constants (LaunchConst) that the tier-B kernels stage in LDS.
 constexpr size_t kCounterBytes = 256;
 
-// Occupancy target (waves per SIMD) of the render kernel; RTAMD_WAVES overrides (1..4) for A/B
-// measurements. The defaults (launch_philox) are measured.
-int waves_target(int dflt) {
-  const char* e = std::getenv("RTAMD_WAVES");
-  const int w = e ? std::atoi(e) : dflt;
-  return (w >= 1 && w <= 4) ? w : dflt;
-}
-// (the render kernels live in one translation unit per variant: rt_k_*.hip)
-// (skip: the F_SKIP instantiation, an adaptive frame's launches)
-// (pk: the LDS-staged 4-wide kernels' packed-key instantiation, wide_keys_packed)
-const void* philox_kernel(unsigned var, int loop, bool lds, int w, bool count, bool skip, bool leaf_lds = false,
-                          bool q = false, bool pk = false) {
-  if (var == kVarSpheres) {
-    // (the 4-wide tree from global memory, 128-byte nodes: its own unit, rt_k_spheres_global.hip)
-    if (loop == 2 && !lds && !count && !q && !std::getenv("RTAMD_NO_COLD")) return rt::philox_kernel_spheres_global(w, skip);
-    return rt::philox_kernel_spheres(loop, lds, w, count, leaf_lds, q, skip, pk);
-  }
-  if (var == kVarCornell) return rt::philox_kernel_cornell(loop, lds, w, count, leaf_lds, skip, pk);
-  if (var == kVarFullDark) return rt::philox_kernel_full_dark(loop, lds, w, count, skip);
-  return rt::philox_kernel_full(loop, lds, w, count, skip);
-}
-bool env_off(const char* name) {
-  const char* e = std::getenv(name);
-  return e && e[0] == '0';
+// The render kernel of a form (the kernels live in one translation unit per variant or form: rt_k_*.hip).
+const void* philox_kernel(const rt::KernelForm& f) {
+  if (f.unit == rt::kUnitSpheresPacked) return rt::philox_kernel_spheres_packed(f);
+  if (f.unit == rt::kUnitSpheresGlobal) return rt::philox_kernel_spheres_global(f);
+  if (f.unit == rt::kUnitCountPacked) return rt::philox_kernel_count_packed(f);
+  if (f.var == kVarSpheres) return rt::philox_kernel_spheres(f);
+  if (f.var == kVarCornell) return rt::philox_kernel_cornell(f);
+  return f.var == kVarFullDark ? rt::philox_kernel_full_dark(f) : rt::philox_kernel_full(f);
 }
 // The largest 4-wide tree an LDS-staged launch can be given: its 128-byte nodes alone within the budget
 // (whatever the waves, stacks and leaf table take comes off that).
-constexpr int kLdsMaxWideNodes = (int)((kLdsBudget - kLcBytes) / sizeof(rt_wnode));
+constexpr int kLdsMaxWideNodes = (int)((rt::kLdsBudget - kLcBytes) / sizeof(rt_wnode));
 // Every LDS-staged tree is within the packed sort keys' id bound (include/rt_wide.h), with its at most 4
-// leaf slots per node; wide_keys_packed still checks the uploaded world's own counts.
+// leaf slots per node; rt::wide_keys_packed still checks the uploaded world's own counts.
 static_assert(4 * kLdsMaxWideNodes <= RT_WKEY_MAX_IDS, "an LDS-staged 4-wide tree fits the packed keys");
-// wide_node's packed-key form for this world's 4-wide walks (RTAMD_PACKED_KEYS=0: the key / reference pairs,
-// for A/B runs): the LDS-staged kernels, the counting build of a world they render, and the closest-hits probe.
-bool wide_keys_packed(const rt_ctx* c) {
-  return c->d_wnodes && rt_wkey_fits(c->n_wnodes, c->n_leaves) && !env_off("RTAMD_PACKED_KEYS");
-}
 template <bool LDS>
 const void* exact_variant_l(unsigned f, bool shared_libm) {
   switch (variant_for(f)) {
@@ -371,15 +299,15 @@ unsigned exact_blocks(int width) {
 // The tier-A kernel for the ctx's scene and its dynamic LDS bytes: the node array staged in LDS when it
 // fits beside the static lane stacks (RTAMD_EXACT_LDS=0: never).
 int exact_launch(rt_ctx* c, bool shared_libm, const void** fn, size_t* bytes) {
-  const size_t need = (size_t)c->n_nodes * sizeof(rt_node);
+  const size_t need = (size_t)c->shape.n_nodes * sizeof(rt_node);
   const size_t budget = 160 * 1024 - (size_t)RT_STACK * RT_BLOCK * sizeof(int);
   const char* e = std::getenv("RTAMD_EXACT_LDS");
   if (need <= budget && !(e && e[0] == '0')) {
-    *fn = exact_variant_l<true>(c->features, shared_libm);
+    *fn = exact_variant_l<true>(c->shape.features, shared_libm);
     *bytes = need;
     HIPCHK(hipFuncSetAttribute(*fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
   } else {
-    *fn = exact_variant_l<false>(c->features, shared_libm);
+    *fn = exact_variant_l<false>(c->shape.features, shared_libm);
     *bytes = 0;
   }
   return RT_OK;
@@ -397,27 +325,18 @@ int launch_combine(rt_ctx* c, const LaunchConst& A, hipStream_t st, double* mome
   return RT_OK;
 }
 
-// The launch's culling flags: the caller's, with the per-axis test alone for far-box worlds (rt_ctx::far_boxes).
-uint32_t cull(const rt_ctx* c, uint32_t flags) { return flags | (c->far_boxes ? RT_FLAG_REFERENCE_CULL : 0u); }
+// The launch's culling flags: the caller's, with the per-axis test alone for far-box worlds (WorldShape::far_boxes).
+uint32_t cull(const rt_ctx* c, uint32_t flags) { return flags | (c->shape.far_boxes ? RT_FLAG_REFERENCE_CULL : 0u); }
 
-// The work geometry of a tier-B launch in its constants: the frame's part (shard `rank` of `shards`, the
-// tiles, the sample chunks and their divisors) ...
-void fill_frame_geometry(LaunchConst& A, const rt_render_params* p, int rank, int shards, long long& per_shard) {
-  A.W = p->width;
-  A.H = p->height;
-  A.spp = p->spp;
-  long long tiles_total, slab;
-  geometry(p, A.tile, A.tiles_x, tiles_total, per_shard, slab);
-  A.tiles_total = (int)tiles_total;
-  A.shard_rank = rank;
-  A.shard_count = shards;
-  A.slab = slab;
-  A.chunk = rt_sample_chunk((int64_t)p->width * p->height, p->spp);
-  // RTAMD_CHUNK: another chunk size, for timing experiments only (it changes the summation order,
-  // so the image no longer follows rt.h's tier-B definition)
-  if (const char* ce = std::getenv("RTAMD_CHUNK")) A.chunk = std::max(1, std::min(p->spp, std::atoi(ce)));
-  A.chunks = (p->spp + A.chunk - 1) / A.chunk;
-  A.work_total = slab * A.chunks;  // (the whole frame's; each chunk batch's launch sets its own)
+// The work geometry of a tier-B launch in its constants: the frame's part (p's shard, an unsharded frame being
+// shard 0 of 1; the tiles, the sample chunks and their divisors; `chunk_knob`: LaunchKnobs::chunk) ...
+void fill_frame_geometry(LaunchConst& A, const rt_render_params* p, int chunk_knob) {
+  const FrameGeometry g = frame_geometry(p, chunk_knob);
+  A.W = p->width, A.H = p->height, A.spp = p->spp;
+  A.tile = g.tile, A.tiles_x = g.tiles_x, A.tiles_total = (int)g.tiles_total;
+  A.shard_rank = p->shard_rank, A.shard_count = p->shard_count > 0 ? p->shard_count : 1;
+  A.slab = g.slab, A.chunk = g.chunk, A.chunks = g.chunks;
+  A.work_total = g.slab * g.chunks;  // (the whole frame's; each chunk batch's launch sets its own)
   A.items_total = A.work_total;
   A.tail_start = A.work_total;
   A.div_tp = make_udiv((uint32_t)(A.tile * A.tile));
@@ -431,272 +350,105 @@ void fill_batch_geometry(LaunchConst& A, int k0, int nk, long long tail_items) {
   A.chunk_base = k0;
   A.chunks = nk;
   A.items_total = A.slab * nk;
-  const long long tail = std::min(A.items_total, tail_items);
-  A.tail_start = A.items_total - tail;
-  A.work_total = A.items_total + tail * (A.chunk - 1);
+  A.tail_start = A.items_total - std::min(A.items_total, tail_items);
+  A.work_total = launch_units(A.items_total, tail_items, A.chunk);
   A.div_tile = make_udiv((uint32_t)(A.tile * A.tile * nk));
 }
 
-int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int rank, int shards, uint8_t* d_rgb,
-                  double* d_lin, hipStream_t st, unsigned long long* d_work = nullptr,
-                  unsigned long long* d_prof = nullptr, const ChunkSpan& span = ChunkSpan{}) {
-  LaunchConst A{};
+// A launch's constants (the caller has set its outputs: out_rgb, out_lin, work, prof), and the render kernel's
+// own arguments: what a walk step reads, and the constants' device copy, which lives behind the ctx's work
+// counter (kCounterBytes) and is rewritten by launch_setup ahead of every launch, in stream order after the
+// launch before.
+void fill_launch_const(LaunchConst& A, RenderArgs& R, const rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
+                       const ChunkSpan& span, const rt::LaunchPlan& P) {
+  const rt::LaunchKnobs& K = P.knobs;
   A.S = c->scene;
   A.cam = *cam;
-  A.max_depth = p->max_depth;
+  A.max_depth = p->max_depth, A.seed = p->seed;
   A.flags = cull(c, p->flags);
-  long long per_shard;
-  fill_frame_geometry(A, p, rank, shards, per_shard);
-  const long long slab = A.slab;
-  A.seed = p->seed;
+  fill_frame_geometry(A, p, K.chunk);
   A.counter = c->d_counter;
-  A.work = d_work;
-  A.prof = d_prof;
-  A.out_rgb = d_rgb;
-  A.out_lin = d_lin;
   A.skip = span.skip;
-  // The work counter and the chunk-sum buffer are the ctx's: order this launch after the previous
+  A.partial = (double*)c->fb_partial.p;
+  A.acc = span.acc ? span.acc : (double*)c->fb_acc.p;
+  A.tail_buf = (double*)c->fb_tail.p;
+  A.batch = K.batch, A.batch_per_item = P.batch_per_item, A.batch_floor = K.batch_floor;
+  A.trav_stop = K.trav_stop, A.leaf_stop = K.leaf_stop, A.box_first = K.box_first, A.med_batch = K.med_batch;
+  A.rev_tiles = P.rev_tiles;
+  const LaunchConst* d_lc = reinterpret_cast<LaunchConst*>(reinterpret_cast<unsigned char*>(c->d_counter) + kCounterBytes);
+  R = RenderArgs{A.S, d_lc, A.seed, A.flags, A.trav_stop, A.leaf_stop, A.box_first, A.med_batch, A.prof};
+}
+
+// One launch per chunk batch of the plan (stream-ordered; the span's events around all the render launches):
+// the constants' device copy, the render kernel, the tail's sums, the fold into the running sums.
+int run_batches(rt_ctx* c, LaunchConst& A, const LaunchConst* d_lc, const rt::LaunchPlan& P, const ChunkSpan& span,
+                const void* fn, int grid, void** args, hipStream_t st) {
+  hipEvent_t ev_begin = span.ev_begin ? span.ev_begin : c->ev0, ev_end = span.ev_end ? span.ev_end : c->ev1;
+  for (int b0 = 0; b0 < P.chunks_total; b0 += P.per_batch) {
+    const int nk = std::min(P.per_batch, P.chunks_total - b0);
+    const int k0 = span.first + b0;  // the launch's first chunk of the frame
+    fill_batch_geometry(A, k0, nk, P.tail_items);
+    const bool last = b0 + nk == P.chunks_total;
+    A.combine = (k0 > 0 ? 1 : 0) | (last && !span.keep ? 2 : 0);
+    LaunchConst B = A;  // (arguments are copied at launch)
+    void* sargs[] = {&B, &d_lc};  // the constants' device copy, and the work counter back to 0
+    HIPCHK(hipLaunchKernel((const void*)launch_setup, dim3(1), dim3(64), sargs, 0, st));
+    HIPCHK(hipGetLastError());
+    if (b0 == 0) HIPCHK(hipEventRecord(ev_begin, st));
+    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(P.info.block), args, (size_t)P.info.dyn_lds_bytes, st));
+    HIPCHK(hipGetLastError());
+    if (A.tail_start < A.items_total) {
+      void* targs[] = {&B};
+      HIPCHK(hipLaunchKernel(A.skip ? (const void*)tail_combine_skip : (const void*)tail_combine,
+                             dim3((unsigned)((A.items_total - A.tail_start + 255) / 256)), dim3(256), targs, 0, st));
+      HIPCHK(hipGetLastError());
+    }
+    if (last) HIPCHK(hipEventRecord(ev_end, st));
+    const int rc = launch_combine(c, A, st, span.moments);
+    if (rc) return rc;
+  }
+  return RT_OK;
+}
+
+// One tier-B render of p's shard of the ctx's scene on `st`: plan (rt_launch_plan.h), scratch, constants, run.
+int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, uint8_t* d_rgb, double* d_lin,
+                  hipStream_t st, unsigned long long* d_work = nullptr, unsigned long long* d_prof = nullptr,
+                  const ChunkSpan& span = ChunkSpan{}) {
+  rt::LaunchPlan P;
+  int rc = rt::plan_launch(c->shape, *p, span.first, span.count, d_work != nullptr, span.skip != nullptr,
+                           rt::read_knobs(), kLcBytes, P);
+  if (rc) return rc;
+  const void* fn = philox_kernel(P.form);
+  if (!fn) return unsupported("no render kernel is built for this launch's form");
+  // The work counter and the scratch buffers are the ctx's: order this launch after the previous
   // one, whichever stream that was on (on the same stream, stream order already does).
   if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
   c->last_stream = st;
-  // Chunk sums: [chunk][slab pixel][3] doubles, kept on the ctx and grown on demand, at most
-  // kPartialCap bytes (RTAMD_PARTIAL_CAP overrides, for tests): a frame with more chunks renders them
-  // in batches of consecutive chunks, one launch each, and combine_chunks folds each batch into a
-  // running per-pixel sum in chunk order — the sum rt.h defines, whatever the batching.
-  // (the span: the whole frame, or a progressive frame's next chunks)
-  const int frame_chunks = A.chunks;
-  const int span_first = span.first;
-  const int chunks_total = span.count < 0 ? frame_chunks : span.count;  // chunks of this call
-  if (span_first < 0 || chunks_total < 1 || span_first + chunks_total > frame_chunks) return invalid("bad chunk span");
-  hipEvent_t ev_begin = span.ev_begin ? span.ev_begin : c->ev0, ev_end = span.ev_end ? span.ev_end : c->ev1;
-  const size_t per_chunk = (size_t)slab * 3 * sizeof(double);
-  size_t cap = kPartialCap;
-  if (const char* pc = std::getenv("RTAMD_PARTIAL_CAP")) cap = (size_t)std::max(1ll, std::atoll(pc));
-  const int per_batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunks_total, cap / per_chunk));
-  const int batches = (chunks_total + per_batch - 1) / per_batch;
-  {
-    const size_t need = (size_t)per_batch * per_chunk;
-    const size_t need_acc = (batches > 1 && !span.acc) ? per_chunk : 0;
-    if (need > c->partial_bytes || need_acc > c->acc_bytes) {
-      HIPCHK(hipEventSynchronize(c->ev_done));
-      if (need > c->partial_bytes) {
-        (void)hipFree(c->d_partial);
-        c->d_partial = nullptr;
-        c->partial_bytes = 0;
-        ++c->allocs;
-        HIPCHK(hipMalloc((void**)&c->d_partial, need));
-        c->partial_bytes = need;
-      }
-      if (need_acc > c->acc_bytes) {
-        (void)hipFree(c->d_acc);
-        c->d_acc = nullptr;
-        c->acc_bytes = 0;
-        ++c->allocs;
-        HIPCHK(hipMalloc((void**)&c->d_acc, need_acc));
-        c->acc_bytes = need_acc;
-      }
-    }
-    A.partial = c->d_partial;
-    A.acc = span.acc ? span.acc : c->d_acc;
+  const size_t need_acc = span.acc ? 0 : P.acc_bytes;
+  if (P.partial_bytes > c->fb_partial.bytes || need_acc > c->fb_acc.bytes || P.tail_bytes > c->fb_tail.bytes) {
+    HIPCHK(hipEventSynchronize(c->ev_done));
+    if ((rc = grow(c, c->fb_partial, P.partial_bytes)) || (rc = grow(c, c->fb_acc, need_acc)) ||
+        (rc = grow(c, c->fb_tail, P.tail_bytes)))
+      return rc;
   }
-  // The frame's tail (the full variants' replacement loop, kTail in rt_kernels.h; set below with the
-  // loop): the last `tail_items` work-items of each launch are dealt one sample per unit, their colours
-  // summed in sample order afterwards (tail_combine): the sums rt.h defines, whatever the dealing.
-  // RTAMD_TAIL: tail items per CU (default 768, one per lane of 12 waves; 0: no tail).
-  long long tail_items = 0;
-  auto units_of = [&](long long items) { return items + std::min(items, tail_items) * (A.chunk - 1); };
-  // The render kernel's own arguments (args[0] of `run`): what a walk step reads, and the constants'
-  // device copy, which lives behind the ctx's work counter (kCounterBytes) and is rewritten by
-  // launch_setup ahead of every launch, in stream order after the launch before.
+  LaunchConst A{};
   RenderArgs R{};
-  // one launch per chunk batch (stream-ordered; the events span all of them)
-  auto run = [&](const void* fn, dim3 grid, dim3 block, size_t bytes, void** args) -> int {
-    unsigned char* counter_mem = reinterpret_cast<unsigned char*>(c->d_counter);
-    LaunchConst* d_lc = reinterpret_cast<LaunchConst*>(counter_mem + kCounterBytes);
-    R.S = A.S;
-    R.lc = d_lc;
-    R.seed = A.seed;
-    R.flags = A.flags;
-    R.trav_stop = A.trav_stop;
-    R.leaf_stop = A.leaf_stop;
-    R.box_first = A.box_first;
-    R.med_batch = A.med_batch;
-    R.prof = A.prof;
-    // (work-unit indices are 32-bit on the device, and wave claims may run up to one batch per wave
-    // past the end: keep 2^24 of headroom)
-    if (units_of(slab * per_batch) >= (1ll << 32) - (1ll << 24))
-      return invalid("image too large: more than 2^32 - 2^24 work units per shard and launch");
-    const size_t need_tail = (size_t)std::min(slab * per_batch, tail_items) * (size_t)A.chunk * 3 * sizeof(double);
-    if (need_tail > c->tail_bytes) {
-      HIPCHK(hipEventSynchronize(c->ev_done));
-      (void)hipFree(c->d_tail);
-      c->d_tail = nullptr;
-      c->tail_bytes = 0;
-      ++c->allocs;
-      HIPCHK(hipMalloc((void**)&c->d_tail, need_tail));
-      c->tail_bytes = need_tail;
-    }
-    A.tail_buf = c->d_tail;
-    for (int b0 = 0; b0 < chunks_total; b0 += per_batch) {
-      const int nk = std::min(per_batch, chunks_total - b0);
-      const int k0 = span_first + b0;  // the launch's first chunk of the frame
-      fill_batch_geometry(A, k0, nk, tail_items);
-      const bool last = b0 + nk == chunks_total;
-      A.combine = (k0 > 0 ? 1 : 0) | (last && !span.keep ? 2 : 0);
-      {  // the constants' device copy, and the work counter back to 0
-        LaunchConst B = A;
-        void* sargs[] = {&B, &d_lc};
-        HIPCHK(hipLaunchKernel((const void*)launch_setup, dim3(1), dim3(64), sargs, 0, st));
-        HIPCHK(hipGetLastError());
-      }
-      if (b0 == 0) HIPCHK(hipEventRecord(ev_begin, st));
-      HIPCHK(hipLaunchKernel(fn, grid, block, args, bytes, st));  // (arguments are copied at launch)
-      HIPCHK(hipGetLastError());
-      if (A.tail_start < A.items_total) {
-        LaunchConst B = A;
-        void* targs[] = {&B};
-        HIPCHK(hipLaunchKernel(A.skip ? (const void*)tail_combine_skip : (const void*)tail_combine, dim3((unsigned)((A.items_total - A.tail_start + 255) / 256)),
-                               dim3(256), targs, 0, st));
-        HIPCHK(hipGetLastError());
-      }
-      if (last) HIPCHK(hipEventRecord(ev_end, st));
-      const int rc = launch_combine(c, A, st, span.moments);
-      if (rc) return rc;
-    }
-    return RT_OK;
-  };
-  const char* stop_env = std::getenv("RTAMD_TRAV_STOP");
-  // refill when at most trav_stop/64 of a wave's live lanes still walk (measured: C2 flat at 2-8,
-  // -4 % at 16; the 100k-sphere C5 tree, walks ~3x longer, best at 16)
-  // (the full variant's walks over the caller's tree: 16 in round 2, C4 1496 vs 1567 ms at 200 spp; with
-  // the mixed walk (round 3) 8: C4 at 100 spp 323.7 vs 326.0 ms, 24: 334.0)
-  // Work-items a wave claims per atomic: one claim per batch instead of one per acquisition round
-  // (RTAMD_BATCH; 1 = the lanes' exact need every time). The batch tapers as the frame runs out: a
-  // wave claims at most rem / (16 * waves) items when about `rem` remain, so the waves' unstarted
-  // claims together never exceed 1/16 of what is left.
-  {
-    const char* be = std::getenv("RTAMD_BATCH");
-    A.batch = be ? std::max(1, std::min(4096, std::atoi(be))) : 1024;
-    const double waves = (double)c->cu_count * 4 * 4;  // at most 4 waves per SIMD
-    A.batch_per_item = (float)(1.0 / (16.0 * waves));
-    // ... but never below one item per lane of the claiming wave (RTAMD_BATCH_FLOOR): near the end of
-    // a frame the taper otherwise shrinks claims to the lanes' exact need, one contended atomic per
-    // few items; 64 items are consumed by the wave's lanes in parallel, so they hoard nothing (C2
-    // per shard at N = 8: 21.05 -> 19.95 ms, 0.83 -> 0.88 of ideal; N = 1 140.7 -> 139.3 ms; 256:
-    // 21.2 ms, 512: 26 ms). Not for the full variant, whose items are long and uneven (C4 at 100
-    // spp with 128: 286 -> 293 ms): 0 there.
-    const char* bf = std::getenv("RTAMD_BATCH_FLOOR");
-    A.batch_floor = bf ? std::max(0, std::min(1024, std::atoi(bf))) : (is_full(variant_for(c->features)) ? 0 : 64);
+  A.out_rgb = d_rgb, A.out_lin = d_lin, A.work = d_work, A.prof = d_prof;
+  fill_launch_const(A, R, c, cam, p, span, P);
+  const int lds = P.info.dyn_lds_bytes;
+  if (lds) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  int grid = P.info.grid, n_items = P.n_items, entries = P.entries, n_leaves = P.n_leaves;
+  if (!P.form.lds) {  // (at most the blocks that are resident at once)
+    int bpc = 1;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, P.info.block, (size_t)lds));
+    grid = (int)std::min<long long>(grid, (long long)c->cu_count * std::max(1, bpc));
   }
-  A.trav_stop = stop_env ? std::max(0, std::min(63, std::atoi(stop_env)))
-                         : (c->n_nodes > 20000 ? 16 : 8);
-  const char* leaf_env = std::getenv("RTAMD_LEAF_STOP");
-  // leaf steps once <= that many lanes still seek their first leaf (measured: C2 212.6 ms at 6-8/64
-  // vs 219.7 at 0 and 232 without postponement; C5 (16 spp) 219.9 ms at 16/64 vs 326 at 0)
-  A.leaf_stop = leaf_env ? std::max(0, std::min(64, std::atoi(leaf_env))) : A.trav_stop;
-  // binary walks of the full variant (media / frame worlds, C4): box-only steps while more than
-  // box_first/64 of the live lanes are at BVH nodes (4-wide nodes count; measured on C4 at 100 spp, round
-  // 2: 64 (never) 430 ms, 48 416, 32 406, 16 398, 8 413; round 5, hoisted media and one 4-wide tree, with
-  // trav_stop 8: 0 189.6, 2 178.6, 4 174.6, 8 176.3, 16 182.3, 32 185.3; C3's Cornell kernel does not
-  // take it)
-  const char* box_env = std::getenv("RTAMD_BOX_FIRST");
-  A.box_first = box_env ? std::max(0, std::min(64, std::atoi(box_env))) : 4;
-  const char* med_env = std::getenv("RTAMD_MED_BATCH");
-  // lanes at a medium wait for med_batch of them (round 4, C4 at 100 spp: 0 249.0 ms, 4 245.3, 8 245.9,
-  // 16 295). Since round 5 a world's own media are hoisted (RT_BVH_MEDIA_FIRST, taken where walks start):
-  // only media inside instance frames still wait here, none in C4 (0 174.6 ms vs 4 176.3): off by default
-  A.med_batch = med_env ? std::max(0, std::min(64, std::atoi(med_env))) : 0;
-  // work order only (the chunk sums do not depend on it): the slab's tiles last to first
-  A.rev_tiles = env_off("RTAMD_TILE_REV") || !std::getenv("RTAMD_TILE_REV") ? 0u : (uint32_t)per_shard;
-  const unsigned var = variant_for(c->features);
-  const bool count = d_work != nullptr;
-  const bool skip = A.skip != nullptr;  // (an adaptive frame: the F_SKIP kernels, which test its mask)
-  if (skip && count) return invalid("the counting build has no adaptive-frame kernels");
-  // Replacement loop (RTAMD_REPLACE=0 disables) for every world whose instance frames nest at most
-  // RT_MAX_FRAMES deep; worlds with media or frames walk the caller's tree in the reference's order.
-  // Over the 4-wide tree when one was built (RTAMD_WIDE=0 disables; the reference-cull flag asks
-  // for the binary tree's exact box test).
-  const bool replace = c->replace_ok && !env_off("RTAMD_REPLACE");
-  // The wide tree pays off on rebuilt (>= 16-leaf) worlds; small worlds keep the binary walk
-  // (Cornell: 409 vs 262-399 Msamples/s measured), RTAMD_WIDE=1 forces it.
-  const char* wenv = std::getenv("RTAMD_WIDE");
-  const bool want_wide = wenv ? wenv[0] != '0' : c->rebuilt_bvh;
-  // (the full variant has no 4-wide instantiation: its media-free worlds walk the binary tree)
-  const bool wide = replace && c->d_wnodes && !(A.flags & RT_FLAG_REFERENCE_CULL) && want_wide && !is_full(var);
-  const int loop = wide ? 2 : (replace ? 1 : 0);
-  if (loop && is_full(var)) {  // (kTail kernels; the per-sample loop claims whole work-items)
-    const char* te = std::getenv("RTAMD_TAIL");
-    tail_items = (long long)c->cu_count * (te ? std::max(0, std::min(1 << 16, std::atoi(te))) : 768);
-  }
-  // waves per SIMD (measured): spheres 4 when the LDS-staged kernel fits at 4 (C2 158.4 ms vs
-  // 166.6 at 3, 203.2 at 2), else 3 (C5 186.7 ms vs 228.5 at 4, -15 % at 2); Cornell-like on the
-  // replacement loop 3 (C3 359.6 ms vs 374.3 at 4, 453.3 at 2), 1 on the per-sample loop; full
-  // variant on the replacement loop 3 (C4 at 100 spp: 90.9 vs 87.5 Msamples/s at 2), on the
-  // per-sample loop 2 despite 784 B/lane of scratch (C4 35.2 vs 23.4 at 1 wave, 9.1 at 3)
-  int waves = (var == kVarSpheres || loop) ? waves_target(3) : waves_target(is_full(var) ? 2 : 1);
-  // Side slots after the stacks, then the 4 lane ints philox_loop2 keeps in LDS (RT_LANE_LDS)
-  const int side_ints = side_ints_of(var, c->scene.frames, loop) + (lane_lds_of(var, loop) ? 4 : 0);
-  // LDS-staged kernel when the traversal's node array plus the stacks fit one CU's 160 KiB
-  // (RTAMD_LDS=0 disables it for A/B runs).
-  // (the counting build walks from global memory; it only learns here whether the timed launch of this world
-  // takes the packed 4-wide kernels, whose walk it then counts: count_pk)
-  bool count_pk = false;
-  if (!env_off("RTAMD_LDS") && (!is_full(var) || loop)) {
-    const int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;  // (wide_node writes 3 slots)
-    const int items = wide ? c->n_wnodes : c->n_nodes;
-    const size_t rec = wide ? sizeof(rt_wnode) : sizeof(rt_node);
-    const bool leaf_lds = wide && !env_off("RTAMD_LEAF_LDS");  // RTAMD_LEAF_LDS=0: leaves never in LDS
-    // LDS bytes at `w` waves per SIMD: the launch constants, the nodes, the lane stacks, and the wide
-    // walk's leaf table when it fits as well
-    auto lds_bytes = [&](int w, int& n_leaves) {
-      const size_t b =
-          (size_t)kLcBytes + (size_t)items * rec + (size_t)(entries + side_ints) * (w * 256) * sizeof(int);
-      n_leaves = leaf_lds && b + (size_t)c->n_leaves * sizeof(rt_node) <= kLdsBudget ? c->n_leaves : 0;
-      return b + (size_t)n_leaves * sizeof(rt_node);
-    };
-    int n_leaves = 0;
-    // (and only when there is work for the 4th wave: C1's 20 000 items fill less than 3 waves)
-    if (var == kVarSpheres && !std::getenv("RTAMD_WAVES") && lds_bytes(4, n_leaves) <= kLdsBudget &&
-        (!leaf_lds || n_leaves > 0) && A.work_total >= (long long)c->cu_count * 1024)
-      waves = 4;
-    const int block = waves * 256;
-    const size_t bytes = lds_bytes(waves, n_leaves);
-    if (count) {
-      count_pk = bytes <= kLdsBudget && wide && wide_keys_packed(c);
-    } else if (bytes <= kLdsBudget) {
-      const bool pk = wide && wide_keys_packed(c);
-      const void* fn = philox_kernel(var, loop, true, waves, false, skip, n_leaves > 0, false, pk);
-      c->last_wide_packed = pk;
-      HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      int n_items = items;
-      void* args[] = {&R, &n_items, (void*)&entries, &n_leaves};
-      c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (skip ? F_SKIP : 0u), loop, 1, n_leaves > 0, waves, c->cu_count,
-                                      block, (int)bytes, A.work_total, A.chunk,
-                                      (loop == 2 || (loop == 1 && c->mixed_wide)) ? c->n_wnodes : 0, batches, 0};
-      return run(fn, dim3(c->cu_count), dim3(block), bytes, args);
-    }
-  }
-  // (spheres-only worlds uploaded with RTAMD_QNODE=1 read the 4-wide tree from global memory in its
-  // 64-byte quantised form: A/B only, measured slower)
-  const void* fn = count_pk ? rt::philox_kernel_count_packed(var)
-                            : philox_kernel(var, loop, false, count ? 1 : waves, count, skip, false, loop == 2 && c->d_qnodes);
-  c->last_wide_packed = count_pk;
-  // replacement loops: lane stacks (+ Side slots) in dynamic LDS, sized for this world's stack bound
-  // (wide_node writes 3 slots)
-  int entries = wide ? c->wide_stack_need + 3 : c->stack_need + 2;
-  // (ahead of them the launch constants; the per-sample loop keeps both in static LDS)
-  const size_t dyn = loop ? (size_t)kLcBytes + (size_t)(entries + side_ints) * RT_BLOCK * sizeof(int) : 0;
-  if (loop) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-  int bpc = 1;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, RT_BLOCK, dyn));
-  const long long want = (A.work_total + RT_BLOCK - 1) / RT_BLOCK;
-  const long long resident = (long long)c->cu_count * std::max(1, bpc);
-  const int grid = (int)std::max(1ll, std::min(want, resident));
-  c->last_launch = rt_launch_info{var | (loop == 2 ? F_WIDE : 0u) | (count ? F_COUNT : 0u) | (skip ? F_SKIP : 0u), loop, 0, 0,
-                                  count ? 1 : waves, grid, RT_BLOCK, (int)dyn, A.work_total, A.chunk,
-                                  (loop == 2 || (loop == 1 && c->mixed_wide)) ? c->n_wnodes : 0, batches, 0};
-  void* args[] = {&R, &entries};
-  return run(fn, dim3(grid), dim3(RT_BLOCK), dyn, args);
+  c->last_launch = P.info;
+  c->last_launch.grid = grid;
+  c->last_wide_packed = P.form.pk;
+  void* staged_args[] = {&R, &n_items, &entries, &n_leaves};
+  void* global_args[] = {&R, &entries};
+  return run_batches(c, A, R.lc, P, span, fn, grid, P.form.lds ? staged_args : global_args, st);
 }
 
 // rt_render, tier B, on a multi-device ctx (rt_create_multi): shard r of N = the ctx's r-th device. Every
@@ -707,9 +459,7 @@ int launch_philox(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, in
 int render_multi(rt_ctx* c, const rt_camera* cam, rt_render_params p, uint8_t* out_rgb, double* out_lin) {
   const int n = 1 + (int)c->peers.size();
   p.shard_count = n;
-  int tile, tiles_x;
-  long long tt, ps, slab;
-  geometry(&p, tile, tiles_x, tt, ps, slab);
+  const long long slab = frame_geometry(&p).slab;
   auto dev_ctx = [&](int r) { return r == 0 ? c : c->peers[r - 1]; };
   const long long npx = (long long)p.width * p.height;
   // the send slabs on every device, the gathered slabs and the image on device 0: the ctx's frame buffers,
@@ -739,7 +489,7 @@ int render_multi(rt_ctx* c, const rt_camera* cam, rt_render_params p, uint8_t* o
     DEVICE_SCOPE(d->device);
     rt_render_params pr = p;
     pr.shard_rank = r;
-    if ((rc = launch_philox(d, cam, &pr, r, n, (uint8_t*)d->fb_slab.p, out_lin ? (double*)d->fb_slab_lin.p : nullptr,
+    if ((rc = launch_philox(d, cam, &pr, (uint8_t*)d->fb_slab.p, out_lin ? (double*)d->fb_slab_lin.p : nullptr,
                             d->stream)))
       return rc;
     if (r == 0) HIPCHK(hipEventRecord(c->ev_gather, c->stream));
@@ -822,9 +572,6 @@ int rt_create(int device, rt_ctx** out) {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, c->device));
     c->cu_count = prop.multiProcessorCount;
-    int bpc = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void*)render_philox<F_ALL, 1>, RT_BLOCK, 0));
-    c->blocks_per_cu = bpc;
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
@@ -912,9 +659,6 @@ void rt_destroy(rt_ctx* c) {
   free_scene(c);
   free_frame_bufs(c);
   (void)hipFree(c->d_counter);
-  (void)hipFree(c->d_partial);
-  (void)hipFree(c->d_tail);
-  (void)hipFree(c->d_acc);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_done) (void)hipEventDestroy(c->ev_done);
@@ -924,7 +668,6 @@ void rt_destroy(rt_ctx* c) {
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
-
 
 int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d) { return rt_upload_scene_ex(c, d, 0u); }
 
@@ -964,27 +707,11 @@ int upload_prepared(rt_ctx* c, const rt::PreparedScene& P, const rt_scene_desc* 
   S.world_ref = P.world_ref;
   S.lights = P.lights;
   S.ref_walk = P.ref_walk;
-  S.frames = std::max(1, std::min(RT_MAX_FRAMES, P.frame_depth));
+  c->shape = rt::world_shape(P, c->cu_count);
+  S.frames = c->shape.frames;
   for (int i = 0; i < 3; ++i) S.bg[i] = din->background[i];
-  c->features = P.features;
-  c->n_nodes = (int)P.nodes.size();
   c->n_materials = din->n_materials;
   c->n_textures = din->n_textures;
-  c->n_wnodes = (int)P.wnodes.size();
-  c->n_leaves = (int)P.leaves.size();
-  c->stack_need = P.stack_need;
-  c->wide_stack_need = P.wide_stack_need;
-  c->rebuilt_bvh = P.rebuilt_bvh;
-  // The division-free box test (rt_trace.h box_hit) reads an infinite slab product as the quotient; with
-  // |origin| <= 2^100 (ray_safe) and |d| >= 2^-900 that holds while every finite box coordinate is within
-  // 2^100 (no finite quotient overflows as a product). Worlds beyond it are walked with the reference's
-  // per-axis test alone (RT_FLAG_REFERENCE_CULL), which divides.
-  c->far_boxes = false;
-  for (const rt_node& x : P.nodes)
-    if ((x.type & RT_TYPE_MASK) == RT_NODE_BVH)
-      for (int k = 0; k < 6; ++k) c->far_boxes |= std::isfinite(x.f[k]) && std::fabs(x.f[k]) > 0x1p100;
-  c->mixed_wide = P.mixed_wide;
-  c->replace_ok = P.replace_ok;
   c->has_scene = true;
   return RT_OK;
 }
@@ -1025,12 +752,10 @@ int rt_shard_geometry(const rt_render_params* p, int64_t* tiles_total, int64_t* 
                       int64_t* slab_pixels) {
   int rc = check_params(p);
   if (rc) return rc;
-  int tile, tiles_x;
-  long long tt, ps, sp;
-  geometry(p, tile, tiles_x, tt, ps, sp);
-  if (tiles_total) *tiles_total = tt;
-  if (tiles_per_shard) *tiles_per_shard = ps;
-  if (slab_pixels) *slab_pixels = sp;
+  const FrameGeometry g = frame_geometry(p);
+  if (tiles_total) *tiles_total = g.tiles_total;
+  if (tiles_per_shard) *tiles_per_shard = g.per_shard;
+  if (slab_pixels) *slab_pixels = g.slab;
   return RT_OK;
 }
 
@@ -1043,8 +768,7 @@ int rt_internal_work_units(const rt_render_params* p, int chunk_first, int n_chu
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!out5 || !out_slot))) return invalid("null output");
   LaunchConst A{};
-  long long per_shard;
-  fill_frame_geometry(A, p, p->shard_rank, p->shard_count > 0 ? p->shard_count : 1, per_shard);
+  fill_frame_geometry(A, p, rt::chunk_knob());
   if (chunk_first < 0 || n_chunks < 1 || chunk_first + n_chunks > A.chunks || tail_items < 0)
     return invalid("bad chunk span");
   fill_batch_geometry(A, chunk_first, n_chunks, tail_items);
@@ -1066,6 +790,31 @@ int rt_internal_work_units(const rt_render_params* p, int chunk_first, int n_chu
   return RT_OK;
 }
 
+// Internal (rt_internal.h; no device needed): the launch plan launch_philox would make for `desc` uploaded
+// with `upload_flags` on a device of `cu_count` CUs, under the environment's knobs.
+int rt_internal_launch_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p,
+                            int span_first, int span_count, int count_build, int adaptive, rt_launch_info* out,
+                            int32_t* out_extra) {
+  if (!desc || !out || cu_count < 1) return invalid("null argument");
+  int rc = check_params(p);
+  if (rc) return rc;
+  rt::PreparedScene S;
+  if ((rc = rt::prepare_scene(desc, upload_flags, S))) return rc;
+  rt::LaunchPlan P;
+  rc = rt::plan_launch(rt::world_shape(S, cu_count), *p, span_first, span_count, count_build != 0, adaptive != 0,
+                       rt::read_knobs(), kLcBytes, P);
+  if (rc) return rc;
+  *out = P.info;
+  if (out_extra) {
+    const rt::LaunchKnobs& K = P.knobs;
+    const int32_t extra[RT_PLAN_EXTRA] = {
+        P.n_items,     P.entries,           P.n_leaves,           K.trav_stop, K.leaf_stop, K.box_first, K.med_batch, K.batch,
+        K.batch_floor, (int32_t)P.rev_tiles, (int32_t)P.tail_items, P.per_batch, P.form.pk,   P.form.unit, P.info.grid, P.form.waves};
+    std::copy(extra, extra + RT_PLAN_EXTRA, out_extra);
+  }
+  return RT_OK;
+}
+
 int rt_render_shard_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, uint8_t* d_rgb, double* d_lin,
                           void* stream) {
   if (!c || !cam || !d_rgb) return invalid("null argument");
@@ -1077,21 +826,18 @@ int rt_render_shard_async(rt_ctx* c, const rt_camera* cam, const rt_render_param
   }
   if (p->rng_mode != RT_RNG_PHILOX) return invalid("sharded rendering needs RT_RNG_PHILOX (tier B)");
   DEVICE_SCOPE(c->device);
-  const int shards = p->shard_count > 0 ? p->shard_count : 1;
-  return launch_philox(c, cam, p, p->shard_rank, shards, d_rgb, d_lin, (hipStream_t)stream);
+  return launch_philox(c, cam, p, d_rgb, d_lin, (hipStream_t)stream);
 }
 
 int rt_assemble_async(rt_ctx* c, const rt_render_params* p, const uint8_t* d_slabs, uint8_t* d_image, void* stream) {
   if (!c || !d_slabs || !d_image) return invalid("null argument");
   int rc = check_params(p);
   if (rc) return rc;
-  int tile, tiles_x;
-  long long tt, ps, sp;
-  geometry(p, tile, tiles_x, tt, ps, sp);
+  const FrameGeometry g = frame_geometry(p);
   const long long n = (long long)p->width * p->height;
   DEVICE_SCOPE(c->device);  // (the caller's current device may be another ctx's)
   hipLaunchKernelGGL(assemble<uint8_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_slabs,
-                     d_image, p->width, p->height, tile, tiles_x, p->shard_count > 0 ? p->shard_count : 1, sp);
+                     d_image, p->width, p->height, g.tile, g.tiles_x, p->shard_count > 0 ? p->shard_count : 1, g.slab);
   HIPCHK(hipGetLastError());
   return RT_OK;
 }
@@ -1101,13 +847,11 @@ int rt_assemble_linear_async(rt_ctx* c, const rt_render_params* p, const double*
   if (!c || !d_slabs || !d_image) return invalid("null argument");
   int rc = check_params(p);
   if (rc) return rc;
-  int tile, tiles_x;
-  long long tt, ps, sp;
-  geometry(p, tile, tiles_x, tt, ps, sp);
+  const FrameGeometry g = frame_geometry(p);
   const long long n = (long long)p->width * p->height;
   DEVICE_SCOPE(c->device);
   hipLaunchKernelGGL(assemble<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_slabs,
-                     d_image, p->width, p->height, tile, tiles_x, p->shard_count > 0 ? p->shard_count : 1, sp);
+                     d_image, p->width, p->height, g.tile, g.tiles_x, p->shard_count > 0 ? p->shard_count : 1, g.slab);
   HIPCHK(hipGetLastError());
   return RT_OK;
 }
@@ -1144,14 +888,12 @@ int rt_render(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, cons
   rt_frame_timing ft{};
   ft.n_devices = 1;
   if (p.rng_mode == RT_RNG_PHILOX) {
-    int tile, tiles_x;
-    long long tt, ps, slab;
-    geometry(&p, tile, tiles_x, tt, ps, slab);
+    const long long slab = frame_geometry(&p).slab;
     if ((rc = grow(c, c->fb_slab, (size_t)slab * 3))) return rc;
     if (out_lin && (rc = grow(c, c->fb_slab_lin, sizeof(double) * (size_t)slab * 3))) return rc;
     const uint8_t* slab_rgb = (const uint8_t*)c->fb_slab.p;
     const double* slab_lin = out_lin ? (const double*)c->fb_slab_lin.p : nullptr;
-    rc = launch_philox(c, cam, &p, 0, 1, (uint8_t*)slab_rgb, (double*)slab_lin, st);
+    rc = launch_philox(c, cam, &p, (uint8_t*)slab_rgb, (double*)slab_lin, st);
     if (!rc) rc = hip_ok(hipEventRecord(c->ev_gather, st), "hipEventRecord");
     if (!rc) rc = rt_assemble_async(c, &p, slab_rgb, d_img, st);
     if (!rc && out_lin) rc = rt_assemble_linear_async(c, &p, slab_lin, d_img_lin, st);
@@ -1181,7 +923,7 @@ int rt_render(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, cons
     const void* fn = nullptr;
     size_t lds = 0;
     if (int rc = exact_launch(c, (p.flags & RT_FLAG_SHARED_LIBM) != 0, &fn, &lds)) return rc;
-    int n_nodes = c->n_nodes;
+    int n_nodes = c->shape.n_nodes;
     HIPCHK(hipEventRecord(c->ev0, st));
     void* args[] = {&A, &n_nodes};
     HIPCHK(hipLaunchKernel(fn, dim3(exact_blocks(p.width)), dim3(RT_BLOCK), args, lds, st));
@@ -1214,16 +956,13 @@ int render_counting(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin
   if (pin->rng_mode != RT_RNG_PHILOX) return invalid("rt_render_work: tier B only");
   DEVICE_SCOPE(c->device);
   rt_render_params p = *pin;
-  const int shards = p.shard_count > 0 ? p.shard_count : 1;
-  int tile, tiles_x;
-  long long tt, ps, slab;
-  geometry(&p, tile, tiles_x, tt, ps, slab);
+  const long long slab = frame_geometry(&p).slab;
   DevBuf slab_buf, work;
   HIPCHK(hipMalloc(&slab_buf.p, (size_t)slab * 3));
   HIPCHK(hipMalloc(&work.p, sizeof(unsigned long long) * (16 + 64)));
   unsigned long long* d_work = (unsigned long long*)work.p;
   HIPCHK(hipMemsetAsync(d_work, 0, sizeof(unsigned long long) * (16 + 64), c->stream));
-  rc = launch_philox(c, cam, &p, p.shard_rank, shards, (uint8_t*)slab_buf.p, nullptr, c->stream, d_work,
+  rc = launch_philox(c, cam, &p, (uint8_t*)slab_buf.p, nullptr, c->stream, d_work,
                      out_prof ? d_work + 16 : nullptr);
   HIPCHK(hipStreamSynchronize(c->stream));
   if (rc) return rc;
@@ -1246,7 +985,6 @@ int rt_render_step_profile(rt_ctx* c, const rt_camera* cam, const rt_render_para
   return render_counting(c, cam, pin, out_work, out_prof);
 }
 
-
 int rt_last_kernel_ms(rt_ctx* c, double* out_ms) {
   if (!c || !out_ms) return invalid("null argument");
   float ms = 0;
@@ -1266,7 +1004,7 @@ int rt_last_launch(rt_ctx* c, rt_launch_info* out) {
 int rt_debug_wide_keys(rt_ctx* c, int out[4]) {
   if (!c || !out) return invalid("null argument");
   out[0] = c->last_wide_packed;
-  out[1] = c->has_scene && c->d_wnodes && rt_wkey_fits(c->n_wnodes, c->n_leaves);
+  out[1] = c->has_scene && c->d_wnodes && rt_wkey_fits(c->shape.n_wnodes, c->shape.n_leaves);
   out[2] = RT_WKEY_BITS;
   out[3] = kLdsMaxWideNodes;
   return RT_OK;
@@ -1314,13 +1052,12 @@ void frame_free(rt_frame* f) {
 
 // Image pixels in the slab of shard (p.shard_rank, p.shard_count): its tiles, clipped to the image.
 long long owned_pixels(const rt_render_params& p) {
-  int tile, tiles_x;
-  long long tt, ps, slab, n = 0;
-  geometry(&p, tile, tiles_x, tt, ps, slab);
+  const FrameGeometry g = frame_geometry(&p);
   const int shards = p.shard_count > 0 ? p.shard_count : 1;
-  for (long long gt = p.shard_rank; gt < tt; gt += shards) {
-    const long long ty = gt / tiles_x, tx = gt % tiles_x;
-    n += std::min<long long>(tile, p.width - tx * tile) * std::min<long long>(tile, p.height - ty * tile);
+  long long n = 0;
+  for (long long gt = p.shard_rank; gt < g.tiles_total; gt += shards) {
+    const long long ty = gt / g.tiles_x, tx = gt % g.tiles_x;
+    n += std::min<long long>(g.tile, p.width - tx * g.tile) * std::min<long long>(g.tile, p.height - ty * g.tile);
   }
   return n;
 }
@@ -1360,8 +1097,7 @@ uint32_t frame_sections(const rt_frame* f) {
 // The frame's geometry and sums in launch constants, for its frame_* helper kernels (rt_kernels.h): the
 // frame's own shard, an unsharded frame being shard 0 of 1.
 void frame_const(const rt_frame* f, LaunchConst& A) {
-  long long per_shard;
-  fill_frame_geometry(A, &f->p, f->p.shard_rank, f->p.shard_count, per_shard);
+  fill_frame_geometry(A, &f->p, rt::chunk_knob());
   A.chunk = f->chunk;  // (rt.h's, whatever RTAMD_CHUNK says: frame_new refuses the override)
   A.acc = f->d_sum;
 }
@@ -1506,9 +1242,7 @@ int frame_new(rt_ctx* c, const rt_camera* cam, const rt_render_params* pin, uint
   f->ctx = c;
   f->cam = *cam;
   f->p = p;
-  int tile, tiles_x;
-  long long tt, ps;
-  geometry(&p, tile, tiles_x, tt, ps, f->slab);
+  f->slab = frame_geometry(&p).slab;
   f->npx = (long long)p.width * p.height;
   f->shard = shard;
   f->owned = shard ? owned_pixels(p) : f->npx;
@@ -1729,7 +1463,7 @@ int rt_frame_advance(rt_frame* f, int max_chunks, int* out_now) {
   span.skip = f->d_skip;
   span.ev_begin = f->events[f->used].first;
   span.ev_end = f->events[f->used].second;
-  rc = launch_philox(c, &f->cam, &f->p, f->p.shard_rank, f->p.shard_count, nullptr, nullptr, c->stream, nullptr,
+  rc = launch_philox(c, &f->cam, &f->p, nullptr, nullptr, c->stream, nullptr,
                      nullptr, span);  // (unsharded: shard 0 of 1)
   if (rc) {  // (some of the step's launches may have been folded in: the sums are no longer a frame's)
     f->valid = false;
@@ -2030,7 +1764,7 @@ int rt_debug_closest_hits(rt_ctx* c, const double* rays, int n, double tmin, dou
     rt::set_error("rt_debug_closest_hits: no scene uploaded");
     return RT_E_STATE;
   }
-  if ((flags & (RT_DEBUG_RESUMABLE | RT_DEBUG_WIDE | RT_DEBUG_QNODE)) && !c->replace_ok)
+  if ((flags & (RT_DEBUG_RESUMABLE | RT_DEBUG_WIDE | RT_DEBUG_QNODE)) && !c->shape.replace_ok)
     return unsupported("rt_debug_closest_hits: the resumable walks need a world without media and frames");
   if ((flags & (RT_DEBUG_WIDE | RT_DEBUG_QNODE)) && !c->d_wnodes)
     return unsupported("rt_debug_closest_hits: no 4-wide tree for this world");
@@ -2052,7 +1786,7 @@ int rt_debug_closest_hits(rt_ctx* c, const double* rays, int n, double tmin, dou
   else if (flags & RT_DEBUG_WIDE) {
     // the wide_node form and ray set-up the render kernels of this world run: packed sort keys when the tree
     // is within their bound, and the spheres-only variant's walk (fp32 reciprocals from the direction)
-    const bool pk = wide_keys_packed(c), sph = variant_for(c->features) == kVarSpheres;
+    const bool pk = rt::wide_keys_packed(c->shape, rt::read_knobs()), sph = variant_for(c->shape.features) == kVarSpheres;
     const void* fn = sph ? (pk ? (const void*)closest_hits<F_UV | F_WIDE, true> : (const void*)closest_hits<F_UV | F_WIDE>)
                          : (pk ? (const void*)closest_hits<F_ALL | F_UV | F_WIDE, true>
                                : (const void*)closest_hits<F_ALL | F_UV | F_WIDE>);
@@ -2109,7 +1843,7 @@ int rt_debug_exact_trace(rt_ctx* c, const rt_camera* cam, const rt_render_params
   const void* fn = nullptr;
   size_t lds = 0;
   if (int rc = exact_launch(c, (p.flags & RT_FLAG_SHARED_LIBM) != 0, &fn, &lds)) return rc;
-  int n_nodes = c->n_nodes;
+  int n_nodes = c->shape.n_nodes;
   void* args[] = {&A, &n_nodes};
   HIPCHK(hipLaunchKernel(fn, dim3(exact_blocks(p.width)), dim3(RT_BLOCK), args, lds, c->stream));
   HIPCHK(hipGetLastError());

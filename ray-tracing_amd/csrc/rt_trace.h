@@ -597,27 +597,9 @@ __device__ __forceinline__ bool traverse(const Scene& S, int root, const Ray& wr
 // ------------------------------------------------------------------ resumable traversal
 // Per-lane LDS slots of the resumable walk over worlds with instance frames (`stride` ints apart):
 // the world ray (restored when the last frame closes), the ids of the open frames, and of the
-// frames around the best hit (Trav::best_level of them).
-// Side ints per lane for frames nesting `frames` deep: the world ray (14), then the open frames and the
-// frames around the best hit. The host sizes the dynamic LDS per scene: C4's two-deep frames take 8 ints
-// per lane fewer than RT_MAX_FRAMES would. (The world ray's reciprocals stored as well, 6 more ints, would
-// spare prep's divisions when the last frame closes, but take C4's kernel past six blocks per CU: 243.8
-// -> 250.1 ms at 100 spp.)
-__host__ __device__ constexpr int side_ints_for(int frames) { return 14 + 2 * frames; }
+// frames around the best hit (Trav::best_level of them). The slot counts (side_ints_for, side_ints_of,
+// lane_lds_of) are rt_layout.h's, where the host's LDS sizing reads them too.
 constexpr int kSideInts = side_ints_for(RT_MAX_FRAMES);
-// The replacement loop's per-lane LDS ints after the walk stack (philox_loop2's layout, launch_philox's
-// sizing — one definition for both): Side slots for the frame kernels on the binary / mixed walk (loop
-// 1), then, with RT_LANE_LDS, the 4 lane ints (pixel, row, chunk end, depth) of the
-// reference-order kernels (RT_LANE_LDS 1) or of every replacement-loop kernel (2).
-#ifndef RT_LANE_LDS
-#define RT_LANE_LDS 1
-#endif
-__host__ __device__ constexpr int side_ints_of(unsigned var, int frames, int loop) {
-  return ((var & F_FRAMES) && loop == 1) ? side_ints_for(frames) : 0;
-}
-__host__ __device__ constexpr bool lane_lds_of(unsigned var, int loop) {
-  return loop >= 1 && (RT_LANE_LDS >= 2 || (RT_LANE_LDS == 1 && (var & (F_MEDIA | F_FRAMES)) != 0));
-}
 struct Side {
   int* p;
   int stride;
