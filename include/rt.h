@@ -888,8 +888,10 @@ int rt_frame_chunking(int64_t pixels, int spp, int* out_chunk, int* out_chunks_t
  * material. Media draws use tier-B stream (seed, pixel_id = ray index, sample 0).
  * flags: RT_FLAG_REFERENCE_CULL as for rendering, plus one walk selector: none = the recursive
  * walk (media and frames allowed); RT_DEBUG_RESUMABLE = the render loop's resumable binary
- * walk; RT_DEBUG_WIDE = the resumable walk over the 4-wide fp32-box tree. The last two need a
- * world without ConstantMedium and instance frames (else RT_E_UNSUPPORTED).
+ * walk (media and frames in the reference's order, frames nesting at most RT_MAX_FRAMES deep, else
+ * RT_E_UNSUPPORTED); RT_DEBUG_WIDE = the resumable walk over the 4-wide fp32-box tree, which, like
+ * RT_DEBUG_QNODE, needs a world without ConstantMedium and instance frames (else RT_E_UNSUPPORTED,
+ * checked before anything is allocated or launched).
  */
 #define RT_DEBUG_RESUMABLE 4u
 #define RT_DEBUG_WIDE 8u

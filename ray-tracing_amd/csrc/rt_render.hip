@@ -1766,6 +1766,10 @@ int rt_debug_closest_hits(rt_ctx* c, const double* rays, int n, double tmin, dou
   }
   if ((flags & (RT_DEBUG_RESUMABLE | RT_DEBUG_WIDE | RT_DEBUG_QNODE)) && !c->shape.replace_ok)
     return unsupported("rt_debug_closest_hits: the resumable walks need a world without media and frames");
+  // (a mixed-walk world has d_wnodes too: its re-bounded subtrees' trees, which no plain 4-wide walk from
+  // the binary world root may enter)
+  if ((flags & (RT_DEBUG_WIDE | RT_DEBUG_QNODE)) && c->scene.ref_walk)
+    return unsupported("rt_debug_closest_hits: the 4-wide walks need a world without media and instance frames");
   if ((flags & (RT_DEBUG_WIDE | RT_DEBUG_QNODE)) && !c->d_wnodes)
     return unsupported("rt_debug_closest_hits: no 4-wide tree for this world");
   if (n == 0) return RT_OK;

@@ -281,7 +281,8 @@ def _left_first_bound(nodes, node, memo):
 
 
 @pytest.mark.parametrize("name,param", [("random_book_one", 0), ("stress_spheres", 2000), ("stress_spheres", 20000),
-                                        ("random", 0), ("cornell", 0), ("next_week_final", 0), ("spine", 0)])
+                                        ("random", 0), ("cornell", 0), ("next_week_final", 0), ("spine", 0),
+                                        ("zoo:chains", 0), ("zoo:moving", 0), ("zoo:frames", 0), ("zoo:media", 0)])
 def test_stack_bound_covers_every_ray_direction(name, param):
     """rt_tree_stack_need (the bound rt_upload_scene sizes the LDS stacks with) is at least the
     deepest stack the walk reaches over all 8 direction-sign combinations, on the tree the device
@@ -289,6 +290,9 @@ def test_stack_bound_covers_every_ray_direction(name, param):
     import itertools
     if name == "spine":
         scene = _spine_scene()
+    elif name.startswith("zoo:"):  # the builder-made worlds of tests/zoo_worlds.py
+        import zoo_worlds
+        scene = zoo_worlds.build(name[4:]).scene
     else:
         scene, _ = rtamd.make_scene(name, rtamd.randGen(1024), param=param)
     rb = rtamd.rebuilt_scene(scene)
