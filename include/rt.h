@@ -514,6 +514,60 @@ typedef struct rt_launch_info {
 int rt_last_launch(rt_ctx* ctx, rt_launch_info* out);
 
 /*
+ * First-hit feature buffers: per-pixel albedo, normal, depth and coverage of the primary hit, the guide images
+ * of a frame (NaN-free on every bench frame, converged at a handful of samples). Tier B only.
+ *
+ * Definition. For image pixel (px, row) (row 0 = top, as rt_render's outputs) and sample index s, the primary
+ * ray is the one rt_render traces for that sample: stream key = seed, counter {pair, s, pid, 0} with
+ * pid = row*W + px; draws 0 and 1 are ru, rv; u = (px + ru)/W, v = ((H-1-row) + rv)/H; getRay then makes its own
+ * draws (disk rejection pairs, then the time). The closest hit is taken in [kEps, +inf) exactly as the render's
+ * first segment takes it: the same tie rule, the same keyed ConstantMedium draw at the stream position reached
+ * (RT_RNG_PHILOX above), and RT_FLAG_REFERENCE_CULL is honoured. The sample's feature vector is 8 doubles:
+ *   albedo[3]  on a hit, textureValue of the hit material's texture at the hit's (u, v, p) for Lambertian, Metal,
+ *              DiffuseLight (front or back face) and Isotropic, (1,1,1) for Dielectric; on a miss the background;
+ *   normal[3]  the hit record's normal as faceNormal leaves it (a medium hit keeps the reference's fixed normal);
+ *              0 on a miss;
+ *   depth      t * sqrt(dot(d, d)), with the project's dot order (x*x + y*y + z*z) and no contraction; 0 on a miss;
+ *   hits       1.0 or 0.0.
+ * sums[pixel][k] is the left fold, in sample order, of the vectors of samples first_sample .. first_sample +
+ * n_samples - 1, starting from 0, or from the caller's buffer when `accumulate` is set. A plain sample-order fold,
+ * unlike the image's chunk order: a lane holds a pixel's eight sums in registers for all its samples (no chunk
+ * sums), the result does not depend on how a caller splits the sample range, and a progressive caller can add
+ * [k0, k1) onto what it has. Of rt_render_params the pass reads width, height, seed, rng_mode, flags
+ * (RT_FLAG_REFERENCE_CULL) and the shard fields; spp, max_depth and the NaN flags are not read.
+ *
+ * rt_render_features        blocking; sums is host memory, [H][W][RT_FEATURE_DOUBLES], read first when accumulating.
+ * rt_render_features_async  the same pass queued on `stream` into device memory in image order (on the ctx's device).
+ * RT_E_INVALID, before any HIP call: a null argument, rng_mode != RT_RNG_PHILOX, RT_FLAG_SHARED_LIBM,
+ * shard_count > 1 (shards are out of scope here: a feature pass covers the whole image), first_sample < 0,
+ * n_samples < 1, first_sample + n_samples beyond INT32_MAX, a frame of 2^32 pixels or more. RT_E_STATE without a
+ * scene. A multi-device ctx runs the pass on its first device. The launch is ordered after the ctx's previous
+ * tier-B launch and before its next, whichever streams they use; a feature pass between two renders leaves the
+ * renders' bytes unchanged.
+ * rt_last_feature_launch    which kernel form the last feature pass ran: variant = the walk's feature bits, loop =
+ *                           2 the 4-wide walk (spheres-only worlds with a 4-wide tree), 1 the mixed resumable walk
+ *                           (every other world whose frames nest at most 4 deep), 0 the recursive walk; LDS staging,
+ *                           waves, grid, block, dynamic LDS bytes; work_items = the frame's 8x8 pixel blocks (a wave
+ *                           folds one block at a time, a lane one pixel); chunk = 0, chunk_batches = 1.
+ * rt_features_resolve       host only, no device: from sums of n_samples >= 1 samples over `pixels` >= 1 pixels,
+ *                           albedo and normal = sum / n (one IEEE division, as the image's average; the normal is
+ *                           not renormalised), depth = depth sum / hits (+inf where hits is 0), coverage = hits / n,
+ *                           and the albedo's bytes through scaleColor (NaN -> 0). Every output may be NULL (skipped).
+ */
+#define RT_FEATURE_DOUBLES 8
+#define RT_FEAT_ALBEDO 0
+#define RT_FEAT_NORMAL 3
+#define RT_FEAT_DEPTH 6
+#define RT_FEAT_HITS 7
+int rt_render_features(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, int first_sample, int n_samples,
+                       int accumulate, double* sums);
+int rt_render_features_async(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, int first_sample,
+                             int n_samples, int accumulate, double* d_sums, void* stream);
+int rt_last_feature_launch(rt_ctx* ctx, rt_launch_info* out);
+int rt_features_resolve(const double* sums, int64_t pixels, int n_samples, double* out_albedo, double* out_normal,
+                        double* out_depth, double* out_coverage, uint8_t* out_albedo_rgb8);
+
+/*
  * Progressive tier-B frames: the image of rt_render, rendered a few sample chunks at a time.
  * A frame holds the running per-pixel sums of the chunks rendered so far (RT_RNG_PHILOX above: chunk
  * sums added in chunk order from 0), so that a caller can look at the image while it converges, stop

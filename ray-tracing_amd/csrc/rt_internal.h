@@ -78,6 +78,14 @@ extern "C" int rt_internal_launch_plan(const rt_scene_desc* desc, uint32_t uploa
                                        const rt_render_params* p, int span_first, int span_count, int count_build,
                                        int adaptive, rt_launch_info* out, int32_t* out_extra);
 
+// The plan of a first-hit feature pass (rt_launch_plan.h plan_features), decided without a device, under the
+// environment's RTAMD_LDS, RTAMD_LEAF_LDS, RTAMD_PACKED_KEYS, RTAMD_WAVES and RTAMD_WIDE: *out = what
+// rt_last_feature_launch would report; out_extra (may be null) = {n_items, entries, n_leaves, wide_packed,
+// leaf_stop}.
+#define RT_FEATURES_PLAN_EXTRA 5
+extern "C" int rt_internal_features_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count,
+                                         const rt_render_params* p, rt_launch_info* out, int32_t* out_extra);
+
 struct rt_builder {
   uint64_t seed, gamma;  // RandGen (SMGen)
   std::vector<rt_node> nodes;

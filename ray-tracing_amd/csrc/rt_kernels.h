@@ -1255,6 +1255,141 @@ __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* 
   }
 }
 
+// ---------------------------------------------------------------- first-hit feature buffers (rt.h rt_render_features)
+// Kernel arguments of a feature pass. Passed by value: the pass has no launch constants of its own to stage.
+struct FeatureArgs {
+  Scene S;
+  rt_camera cam;
+  int W, H;
+  uint32_t flags;  // (RT_FLAG_REFERENCE_CULL)
+  uint64_t seed;
+  int first, count;  // samples first .. first + count - 1 (first + count <= INT32_MAX)
+  int accumulate;    // the fold starts from `sums` instead of 0
+  int leaf_stop;     // walk_until's leaf_stop, /64 of the live lanes (FeaturePlan::leaf_stop: scheduling only)
+  int blocks_x;      // 8x8 pixel blocks per row of blocks, and in the frame
+  unsigned long long blocks_total;
+  unsigned long long* counter;  // the next unclaimed block (0 at launch)
+  double* sums;                 // [H][W][RT_FEATURE_DOUBLES], image order
+};
+
+// The first segment's closest hit in [kEps, +inf), by the sequence the closest_hits probe runs: the resumable
+// walk to its end (stop 0, so the wave's lanes step in lockstep until the last one is done), then the tie redo;
+// REC: the recursive walk. `g` is the sample's own stream after getRay, so a medium's keyed draw sees the
+// position the render's first segment sees.
+template <unsigned F, bool PK, bool REC>
+__device__ __forceinline__ bool first_hit(const Scene& S, const Ray& r, RngPhilox& g, int* stk, int stride, Side& side,
+                                          bool joint, int leaf_stop, Hit& h) {
+  Cnt cnt{};
+  if constexpr (REC) {
+    return traverse<F>(S, S.ref_walk ? S.world_ref : S.world, r, kEps, INFINITY, h, g, stk, joint, cnt, stride);
+  } else {
+    Trav t;
+    trav_begin<F>(t, r, S.world, kEps, INFINITY);
+    if (S.ref_walk) trav_restart_ref(t, S.world, INFINITY);
+    trav_media_first<F>(S, t, kEps, cnt, g, side);
+    bool walking = true;
+    const int live = __popcll(__ballot(true));
+    walk_until<F, PK>(S, t, walking, kEps, stk, stride, joint, 0, (live * leaf_stop) >> 6, cnt, g, side);
+    if (t.tie || (kRefMixed<F> && t.lite)) {
+      trav_redo<F>(t, S.world_ref, INFINITY);
+      if constexpr (kNoInv<F>) t.ray = prep(plain(t.ray));  // (the redo's binary box tests need 1/d)
+      while (trav_step<F>(S, t, kEps, stk, stride, joint, cnt, g, side)) {
+      }
+    }
+    return trav_finish<F>(S, t, r, kEps, h, side);
+  }
+}
+
+// A wave is one 8x8 pixel block, a lane one pixel: the lane folds the feature vectors of its samples, in sample
+// order, into eight accumulators and stores them once (64 contiguous bytes). Blocks are claimed from the pass's
+// counter, one atomic per wave and block; which wave folds a pixel does not show in its sums. Lanes outside the
+// image idle through the block.
+template <unsigned F, bool PK, bool REC>
+__device__ __forceinline__ void features_loop(const FeatureArgs& A, const Scene& S, int* stk, int stride, int* side_p) {
+  const int lane = threadIdx.x & 63;
+  const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
+  Side side{side_p, stride};
+  for (;;) {
+    unsigned long long b = 0;
+    if (lane == 0) b = atomicAdd(A.counter, 1ull);
+    b = __shfl(b, 0);
+    if (b >= A.blocks_total) break;
+    const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
+    const int px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    if (px >= A.W || row >= A.H) continue;  // (idles until the wave's next claim)
+    const uint32_t pid = (uint32_t)((long long)row * A.W + px);
+    double* q = A.sums + (size_t)pid * RT_FEATURE_DOUBLES;
+    double acc[RT_FEATURE_DOUBLES];
+#pragma unroll
+    for (int k = 0; k < RT_FEATURE_DOUBLES; ++k) acc[k] = A.accumulate ? q[k] : 0.0;
+    const int s_end = A.first + A.count;
+    for (int s = A.first; s < s_end; ++s) {
+      RngPhilox g;
+      g.init(A.seed, pid, (uint32_t)s);
+      g.reserve(3);  // the UV pair and the first disk try
+      const double ru = g.draw(), rv = g.draw();
+      const int y = A.H - 1 - row;
+      const double u = ((double)px + ru) / (double)A.W;
+      const double v = ((double)y + rv) / (double)A.H;
+      const Ray ray = get_ray(A.cam, u, v, g);
+      Hit h;
+      double f[RT_FEATURE_DOUBLES] = {A.S.bg[0], A.S.bg[1], A.S.bg[2], 0.0, 0.0, 0.0, 0.0, 0.0};
+      if (first_hit<F, PK, REC>(S, ray, g, stk, stride, side, joint, A.leaf_stop, h)) {
+        // textureValue for every material that has a texture, a DiffuseLight's front face included (so not
+        // hit_texture, which leaves that one out); the kernel's one copy of the texture code
+        const DMat m = S.mats[h.mat];
+        const V3 a = m.type == RT_MAT_DIELECTRIC ? v3(1.0, 1.0, 1.0) : texture_value<F>(S, m.tex, h.u, h.v, h.p);
+        f[RT_FEAT_ALBEDO] = a.x, f[RT_FEAT_ALBEDO + 1] = a.y, f[RT_FEAT_ALBEDO + 2] = a.z;
+        f[RT_FEAT_NORMAL] = h.n.x, f[RT_FEAT_NORMAL + 1] = h.n.y, f[RT_FEAT_NORMAL + 2] = h.n.z;
+        f[RT_FEAT_DEPTH] = h.t * sqrt(dot(ray.d, ray.d));
+        f[RT_FEAT_HITS] = 1.0;
+      }
+#pragma unroll
+      for (int k = 0; k < RT_FEATURE_DOUBLES; ++k) acc[k] = acc[k] + f[k];
+    }
+#pragma unroll
+    for (int k = 0; k < RT_FEATURE_DOUBLES; ++k) q[k] = acc[k];
+  }
+}
+
+// From global memory: the lane stacks (and Side slots) in static LDS at their maxima, as the closest_hits probe.
+template <unsigned F, bool PK, bool REC>
+__global__ void __launch_bounds__(RT_BLOCK) render_features(FeatureArgs A) {
+  __shared__ int stk_mem[(lane_ints<F>() + 1) * RT_BLOCK];
+  features_loop<F, PK, REC>(A, A.S, &stk_mem[threadIdx.x],  RT_BLOCK,
+                            &stk_mem[(((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK) + 1) * RT_BLOCK + threadIdx.x]);
+}
+
+// LDS-staged 4-wide walk (spheres-only worlds): the wide nodes, the leaf table (LEAF_LDS, its own instantiation
+// as in render_philox2_lds) and the lane stacks, `stack_entries` per lane, copied once per workgroup of up to 16
+// waves; the block size is the launch's (1 to 4 waves per SIMD).
+template <unsigned F, bool LEAF_LDS, bool PK>
+__global__ void __launch_bounds__(1024) render_features_lds(FeatureArgs A, int n_nodes, int stack_entries, int n_leaves) {
+  static_assert((F & F_WIDE) != 0 && (F & F_FRAMES) == 0, "the spheres-only 4-wide walk");
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  constexpr int rec = (int)sizeof(rt_wnode), lrec = (int)sizeof(rt_node);
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(A.S.wnodes);
+    uint4* dst = reinterpret_cast<uint4*>(lds);
+    const int n16 = n_nodes * (rec / 16);
+    for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    if constexpr (LEAF_LDS) {
+      const uint4* lsrc = reinterpret_cast<const uint4*>(A.S.leaves);
+      uint4* ldst = reinterpret_cast<uint4*>(lds + (size_t)n_nodes * rec);
+      const int l16 = n_leaves * (lrec / 16);
+      for (int i = threadIdx.x; i < l16; i += blockDim.x) ldst[i] = lsrc[i];
+    }
+  }
+  __syncthreads();
+  Scene S = A.S;
+  S.wnodes = reinterpret_cast<const rt_wnode*>(lds);
+  if constexpr (LEAF_LDS) S.leaves = reinterpret_cast<const rt_node*>(lds + (size_t)n_nodes * rec);
+  else n_leaves = 0;
+  int* stk = reinterpret_cast<int*>(lds + (size_t)n_nodes * rec + (size_t)n_leaves * lrec) + threadIdx.x;
+  (void)stack_entries;  // (the host sizes the LDS with it: plan_features)
+  features_loop<F, PK, false>(A, S, stk, (int)blockDim.x, stk);  // (no frames: the Side slots are never touched)
+}
+
 // ---------------------------------------------------------------- debug: per-function probes
 // The hot-path functions one at a time on device inputs (rt_debug_probe; layouts in rt.h and
 // oracle/oracle.c oracle_probe): record i draws from its own tier-B Philox stream (key = seed, pid = i,
@@ -1442,4 +1577,5 @@ const void* philox_kernel_count_packed(const KernelForm& f);    // rt_k_count_pa
 const void* philox_kernel_cornell(const KernelForm& f);
 const void* philox_kernel_full(const KernelForm& f);
 const void* philox_kernel_full_dark(const KernelForm& f);
+const void* features_kernel(const FeaturePlan& P);  // rt_k_features.hip (render_features / render_features_lds)
 }  // namespace rt

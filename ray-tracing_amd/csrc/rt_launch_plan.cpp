@@ -197,4 +197,51 @@ int plan_launch(const WorldShape& W, const rt_render_params& p, int span_first, 
   return RT_OK;
 }
 
+int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out) {
+  FeaturePlan P;
+  rt_launch_info& I = P.info;
+  const long long blocks = (long long)((p.width + 7) / 8) * ((p.height + 7) / 8);  // (8x8 pixel blocks, one per wave)
+  if ((long long)p.width * p.height >= (1ll << 32)) return invalid("image too large for 32-bit pixel ids");
+  const bool ref_cull = (p.flags & RT_FLAG_REFERENCE_CULL) || W.far_boxes;
+  // The 4-wide walk for the worlds the spheres variant renders over a 4-wide tree (the reference-cull flag asks
+  // for the binary tree's exact box test, RTAMD_WIDE=0 for the binary walk); any other world whose frames nest
+  // at most RT_MAX_FRAMES deep takes the mixed resumable walk, the rest the recursive one.
+  if (variant_for(W.features) == kVarSpheres && W.has_wide && W.replace_ok && !ref_cull && K.wide != 0) P.walk = kFeatWide;
+  else P.walk = W.replace_ok ? kFeatMixed : kFeatRecursive;
+  I.variant = P.walk == kFeatWide ? (kVarSpheres | F_WIDE) : (F_ALL | F_UV | F_MIXW);
+  I.loop = P.walk;
+  I.work_items = blocks, I.chunk = 0, I.chunk_batches = 1;
+  I.wide_nodes = (P.walk == kFeatWide || (P.walk == kFeatMixed && W.mixed_wide)) ? W.n_wnodes : 0;
+  I.block = RT_BLOCK, I.waves = 1, I.dyn_lds_bytes = 0;
+  I.grid = (int)std::max<long long>(1, std::min<long long>((blocks + RT_BLOCK / 64 - 1) / (RT_BLOCK / 64),
+                                                           (long long)W.cu_count * kFeatBlocksPerCU));
+  P.leaf_stop = P.walk == kFeatMixed ? K.box_first : 0;
+  if (P.walk == kFeatWide) {
+    P.leaf_stop = K.leaf_stop >= 0 ? K.leaf_stop : K.trav_stop >= 0 ? K.trav_stop : W.n_nodes > 20000 ? 16 : 8;
+    P.pk = wide_keys_packed(W, K);
+    P.entries = W.wide_stack_need + 3;  // (wide_node writes 3 slots)
+    // LDS-staged like the render's 4-wide kernels: the wide nodes, the leaf table when it fits as well, and the
+    // lane stacks of one workgroup per CU, at the most waves per SIMD (4, or RTAMD_WAVES) that fit kLdsBudget
+    // with the leaves, else with the nodes alone.
+    if (K.lds) {
+      auto lds_bytes = [&](int w, bool leaves) {
+        return (size_t)W.n_wnodes * sizeof(rt_wnode) + (leaves ? (size_t)W.n_leaves * sizeof(rt_node) : 0) +
+               (size_t)P.entries * (w * 256) * sizeof(int);
+      };
+      const int w = K.waves ? K.waves : 4;
+      const bool leaves = K.leaf_lds && W.n_leaves > 0 && lds_bytes(w, true) <= kLdsBudget;
+      if (lds_bytes(w, leaves) <= kLdsBudget) {
+        P.lds = true, P.leaf_lds = leaves;
+        P.n_items = W.n_wnodes, P.n_leaves = leaves ? W.n_leaves : 0;
+        I.waves = w, I.block = w * 256, I.dyn_lds_bytes = (int)lds_bytes(w, leaves);
+        // (one workgroup per CU, fewer when the frame has no block for every wave)
+        I.grid = (int)std::max<long long>(1, std::min<long long>(W.cu_count, (blocks + w * 4 - 1) / (w * 4)));
+      }
+    }
+  }
+  I.lds_staged = P.lds, I.leaf_lds = P.leaf_lds;
+  out = P;
+  return RT_OK;
+}
+
 }  // namespace rt

@@ -95,4 +95,29 @@ struct LaunchPlan {
 int plan_launch(const WorldShape& W, const rt_render_params& p, int span_first, int span_count, bool count_build,
                 bool adaptive, const LaunchKnobs& K, size_t lc_bytes, LaunchPlan& out);
 
+// The launch of a first-hit feature pass (rt.h rt_render_features; kernels: rt_k_features.hip). A wave takes one
+// 8x8 pixel block at a time; `walk` names the closest-hit walk its lanes run, as the closest-hits probe has them.
+enum FeatureWalk : int {
+  kFeatWide = 2,      // spheres-only worlds with a 4-wide tree: the 4-wide walk (LDS-staged, or from global memory)
+  kFeatMixed = 1,     // every other replace_ok world: the F_ALL | F_UV | F_MIXW resumable walk
+  kFeatRecursive = 0  // the rest: the recursive walk
+};
+struct FeaturePlan {
+  int walk = kFeatRecursive;
+  bool lds = false, leaf_lds = false, pk = false;
+  // rt_last_feature_launch: variant = the walk's feature bits, loop = `walk`, work_items = the frame's 8x8 blocks,
+  // chunk = 0, chunk_batches = 1; grid: at most one block per CU (LDS-staged), else at most kFeatBlocksPerCU per CU
+  rt_launch_info info{};
+  int n_items = 0, entries = 0, n_leaves = 0;  // the LDS-staged kernel's trailing int arguments
+  // walk_until's step schedule, /64 of the live lanes, as the render's launch of the same world resolves it
+  // (scheduling only: no result depends on it). 4-wide walk: leaf steps once at most that many lanes still seek
+  // their first leaf (RTAMD_LEAF_STOP, else RTAMD_TRAV_STOP, else 8, or 16 for trees over 20000 nodes); mixed
+  // walk: box-only steps while more lanes than that are at BVH nodes (RTAMD_BOX_FIRST, 4).
+  int leaf_stop = 0;
+};
+constexpr int kFeatBlocksPerCU = 8;  // global-memory forms: RT_BLOCK-thread blocks queued per CU (4 waves per SIMD)
+// Pure, like plan_launch. Reads of `p` the frame size and RT_FLAG_REFERENCE_CULL; of `K` lds, leaf_lds,
+// packed_keys, waves (the LDS-staged form's), wide, and leaf_stop, trav_stop and box_first (FeaturePlan::leaf_stop).
+int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out);
+
 }  // namespace rt

@@ -1,6 +1,7 @@
 // rt_render.hip — the device half of the C ABI (include/rt.h): scene upload, launches, assembly,
 // debug probes. The render kernels are templates in rt_kernels.h, instantiated per scene variant in
-// rt_k_spheres.hip / rt_k_cornell.hip / rt_k_full.hip / rt_k_full_dark.hip.
+// rt_k_spheres.hip / rt_k_cornell.hip / rt_k_full.hip / rt_k_full_dark.hip; the first-hit feature pass's
+// (rt_render_features) in rt_k_features.hip.
 //
 // Kernel design:
 //  * tier B work-items are (pixel, chunk of up to 32 samples): a lane sums its chunk in sample
@@ -61,6 +62,7 @@ struct rt_ctx {
   double last_ms = 0.0;
   rt_launch_info last_launch{};  // rt_last_launch
   int last_wide_packed = 0;      // the last 4-wide walk sorted packed keys (rt_debug_wide_keys)
+  rt_launch_info last_feature{}; // rt_last_feature_launch
   // rt_render's frame events: after the render launches (gather start), after the gather, after assembly
   hipEvent_t ev_gather = nullptr, ev_gathered = nullptr, ev_asm = nullptr;
   rt_frame_timing last_frame{};  // rt_last_frame_timing
@@ -815,6 +817,24 @@ int rt_internal_launch_plan(const rt_scene_desc* desc, uint32_t upload_flags, in
   return RT_OK;
 }
 
+// Internal (rt_internal.h; no device needed): the plan launch_features would make, like rt_internal_launch_plan.
+int rt_internal_features_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p,
+                              rt_launch_info* out, int32_t* out_extra) {
+  if (!desc || !p || !out || cu_count < 1) return invalid("null argument");
+  if (p->width <= 0 || p->height <= 0) return invalid("width and height must be positive");
+  rt::PreparedScene S;
+  int rc = rt::prepare_scene(desc, upload_flags, S);
+  if (rc) return rc;
+  rt::FeaturePlan P;
+  if ((rc = rt::plan_features(rt::world_shape(S, cu_count), *p, rt::read_knobs(), P))) return rc;
+  *out = P.info;
+  if (out_extra) {
+    const int32_t extra[RT_FEATURES_PLAN_EXTRA] = {P.n_items, P.entries, P.n_leaves, P.pk, P.leaf_stop};
+    std::copy(extra, extra + RT_FEATURES_PLAN_EXTRA, out_extra);
+  }
+  return RT_OK;
+}
+
 int rt_render_shard_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, uint8_t* d_rgb, double* d_lin,
                           void* stream) {
   if (!c || !cam || !d_rgb) return invalid("null argument");
@@ -998,6 +1018,92 @@ int rt_last_kernel_ms(rt_ctx* c, double* out_ms) {
 int rt_last_launch(rt_ctx* c, rt_launch_info* out) {
   if (!c || !out) return invalid("null argument");
   *out = c->last_launch;
+  return RT_OK;
+}
+
+namespace {
+// rt_render_features' argument checks (rt.h), before any HIP call; the ctx last, so that every other case can be
+// checked without a device.
+int features_check(const rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int first, int n, const double* sums) {
+  if (!cam || !p || !sums) return invalid("rt_render_features: null argument");
+  if (p->width <= 0 || p->height <= 0) return invalid("rt_render_features: width and height must be positive");
+  if ((long long)p->width * p->height >= (1ll << 32)) return invalid("rt_render_features: a frame of 2^32 pixels or more");
+  if (p->rng_mode != RT_RNG_PHILOX) return invalid("rt_render_features: tier B only (RT_RNG_PHILOX)");
+  if (p->flags & RT_FLAG_SHARED_LIBM) return invalid("rt_render_features: RT_FLAG_SHARED_LIBM is a tier-A flag");
+  if (p->shard_count > 1) return invalid("rt_render_features: shard_count > 1 (a feature pass covers the whole image)");
+  if (first < 0 || n < 1 || (long long)first + n > INT32_MAX)
+    return invalid("rt_render_features: needs first_sample >= 0, n_samples >= 1 and first_sample + n_samples <= INT32_MAX");
+  if (!c) return invalid("rt_render_features: null ctx");
+  if (!c->has_scene) {
+    rt::set_error("rt_render_features: no scene uploaded");
+    return RT_E_STATE;
+  }
+  return RT_OK;
+}
+
+// One feature pass over the whole image on `st`: plan (rt_launch_plan.h plan_features), the block counter back
+// to 0, the kernel. The counter is the ctx's work counter, so the pass takes its place in the ctx's launch
+// order: after the previous tier-B launch (ev_done), and the next one waits for it.
+int launch_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int first, int n, int accumulate,
+                    double* d_sums, hipStream_t st) {
+  rt::FeaturePlan P;
+  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P);
+  if (rc) return rc;
+  const void* fn = rt::features_kernel(P);
+  if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
+  c->last_stream = st;
+  FeatureArgs A{};
+  A.S = c->scene;
+  A.cam = *cam;
+  A.W = p->width, A.H = p->height;
+  A.flags = cull(c, p->flags);
+  A.seed = p->seed;
+  A.first = first, A.count = n, A.accumulate = accumulate;
+  A.leaf_stop = P.leaf_stop;
+  A.blocks_x = (p->width + 7) / 8;
+  A.blocks_total = (unsigned long long)P.info.work_items;
+  A.counter = c->d_counter;
+  A.sums = d_sums;
+  HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), st));
+  const int lds = P.info.dyn_lds_bytes;
+  if (lds) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  int n_items = P.n_items, entries = P.entries, n_leaves = P.n_leaves;
+  void* args[] = {&A, &n_items, &entries, &n_leaves};  // (the global-memory kernels take the first alone)
+  HIPCHK(hipLaunchKernel(fn, dim3(P.info.grid), dim3(P.info.block), args, (size_t)lds, st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_done, st));
+  c->last_feature = P.info;
+  return RT_OK;
+}
+}  // namespace
+
+int rt_render_features_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int first_sample,
+                             int n_samples, int accumulate, double* d_sums, void* stream) {
+  int rc = features_check(c, cam, p, first_sample, n_samples, d_sums);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  return launch_features(c, cam, p, first_sample, n_samples, accumulate, d_sums, (hipStream_t)stream);
+}
+
+int rt_render_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int first_sample, int n_samples,
+                       int accumulate, double* sums) {
+  int rc = features_check(c, cam, p, first_sample, n_samples, sums);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  const size_t bytes = sizeof(double) * RT_FEATURE_DOUBLES * (size_t)p->width * (size_t)p->height;
+  DevBuf buf;
+  HIPCHK(hipMalloc(&buf.p, bytes));
+  if (accumulate) HIPCHK(hipMemcpy(buf.p, sums, bytes, hipMemcpyHostToDevice));
+  rc = launch_features(c, cam, p, first_sample, n_samples, accumulate, (double*)buf.p, c->stream);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(sums, buf.p, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_last_feature_launch(rt_ctx* c, rt_launch_info* out) {
+  if (!c || !out) return invalid("null argument");
+  *out = c->last_feature;
   return RT_OK;
 }
 

@@ -198,7 +198,11 @@ EXPORTED = [
     "rt_frame_shard_state", "rt_frame_save_header", "rt_frame_restore_shard", "rt_debug_wide_keys",
     "rt_frame_checkpoint_info", "rt_checkpoint_resolve", "rt_checkpoint_error", "rt_frame_checkpoint",
     "rt_frame_resume", "rt_frame_resume_shard", "rt_frame_shard_stops", "rt_frame_checkpoint_header",
+    "rt_render_features", "rt_render_features_async", "rt_last_feature_launch", "rt_features_resolve",
 ]
+
+# First-hit feature buffers (rt.h): doubles per pixel of a feature pass's sums, and where each feature starts
+RT_FEATURE_DOUBLES, RT_FEAT_ALBEDO, RT_FEAT_NORMAL, RT_FEAT_DEPTH, RT_FEAT_HITS = 8, 0, 3, 6, 7
 
 # include/rt_wide.h: one 4-wide node (128 B)
 WNODE_DTYPE = np.dtype([("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("child", "<i4", (4,)), ("pad", "<i4", (4,))])
@@ -321,6 +325,11 @@ def lib() -> C.CDLL:
             "rt_frame_resume_shard": (I, [C.c_void_p, C.c_char_p, C.c_size_t, I, I, P(C.c_void_p)]),
             "rt_frame_shard_stops": (I, [C.c_void_p, C.c_void_p]),
             "rt_frame_checkpoint_header": (I, [C.c_void_p, C.c_uint32, I, C.c_char_p, C.c_size_t]),
+            "rt_render_features": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), I, I, I, P(D)]),
+            "rt_render_features_async": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), I, I, I, C.c_void_p,
+                                             C.c_void_p]),
+            "rt_last_feature_launch": (I, [C.c_void_p, P(rt_launch_info)]),
+            "rt_features_resolve": (I, [P(D), C.c_int64, I, P(D), P(D), P(D), P(D), P(C.c_uint8)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -777,6 +786,40 @@ class Context:
         _check(lib().rt_last_launch(self._h, C.byref(info)), "rt_last_launch")
         return {k: getattr(info, k) for k, _ in rt_launch_info._fields_}
 
+    def render_features(self, cam: rt_camera, params: rt_render_params, first_sample: int = 0,
+                        n_samples: Optional[int] = None, into: Optional[np.ndarray] = None) -> np.ndarray:
+        """rt_render_features: the first-hit feature sums of samples first_sample .. first_sample + n_samples - 1
+        (default: params.spp samples), (H, W, 8) doubles: albedo 0:3, normal 3:6, depth 6, hits 7, each the
+        sample-order sum (`resolve_features` makes the images). `into` (H, W, 8, float64, C order) is accumulated
+        onto in place and returned. Blocking."""
+        W, H = params.width, params.height
+        n = params.spp if n_samples is None else n_samples
+        if into is None:
+            sums = np.zeros((H, W, RT_FEATURE_DOUBLES), dtype=np.float64)
+        else:
+            sums = into
+            if sums.dtype != np.float64 or sums.shape != (H, W, RT_FEATURE_DOUBLES) or not sums.flags.c_contiguous:
+                raise RTError("render_features: `into` must be a C-contiguous float64 array of shape (H, W, 8)")
+        _check(lib().rt_render_features(self._h, C.byref(cam), C.byref(params), int(first_sample), int(n),
+                                        int(into is not None), sums.ctypes.data_as(C.POINTER(C.c_double))),
+               "rt_render_features")
+        return sums
+
+    def render_features_async(self, cam, params, d_sums: int, first_sample: int = 0, n_samples: Optional[int] = None,
+                              accumulate: bool = False, stream: int = 0):
+        """rt_render_features_async: the same pass queued on `stream` into device memory (H*W*8 doubles)."""
+        n = params.spp if n_samples is None else n_samples
+        _check(lib().rt_render_features_async(self._h, C.byref(cam), C.byref(params), int(first_sample), int(n),
+                                              int(accumulate), C.c_void_p(d_sums), C.c_void_p(stream or None)),
+               "rt_render_features_async")
+
+    def last_feature_launch(self) -> dict:
+        """rt_last_feature_launch: which kernel form the last feature pass ran (loop 2: the 4-wide walk, 1: the
+        mixed resumable walk, 0: the recursive walk; LDS staging, waves, grid, block, dynamic LDS bytes)."""
+        info = rt_launch_info()
+        _check(lib().rt_last_feature_launch(self._h, C.byref(info)), "rt_last_feature_launch")
+        return {k: getattr(info, k) for k, _ in rt_launch_info._fields_}
+
     def wide_keys(self) -> dict:
         """rt_debug_wide_keys: whether the last 4-wide walk sorted packed keys, whether the uploaded world is
         within their id bound, the reference bits of a packed word, the most 4-wide nodes LDS staging holds."""
@@ -829,6 +872,27 @@ class Context:
                                    y.ctypes.data_as(P(C.c_double)), x.size, out.ctypes.data_as(P(C.c_double))),
                "rt_debug_math")
         return out
+
+
+def resolve_features(sums: np.ndarray, n_samples: int) -> dict:
+    """rt_features_resolve: the guide images of a feature pass's sums (..., 8) over n_samples samples: albedo and
+    normal (..., 3) = sum / n, depth (...) = depth sum / hits (+inf where nothing was hit), coverage (...) =
+    hits / n, albedo_rgb8 (..., 3) the albedo's bytes."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim < 1 or s.shape[-1] != RT_FEATURE_DOUBLES:
+        raise RTError("resolve_features: sums must have 8 doubles per pixel")
+    shape = s.shape[:-1]
+    n = int(np.prod(shape, dtype=np.int64))
+    out = {"albedo": np.zeros(shape + (3,)), "normal": np.zeros(shape + (3,)), "depth": np.zeros(shape),
+           "coverage": np.zeros(shape), "albedo_rgb8": np.zeros(shape + (3,), dtype=np.uint8)}
+    P = C.POINTER
+    _check(lib().rt_features_resolve(s.ctypes.data_as(P(C.c_double)), n, int(n_samples),
+                                     out["albedo"].ctypes.data_as(P(C.c_double)),
+                                     out["normal"].ctypes.data_as(P(C.c_double)),
+                                     out["depth"].ctypes.data_as(P(C.c_double)),
+                                     out["coverage"].ctypes.data_as(P(C.c_double)),
+                                     out["albedo_rgb8"].ctypes.data_as(P(C.c_uint8))), "rt_features_resolve")
+    return out
 
 
 def shard_geometry(params: rt_render_params) -> Tuple[int, int, int]:
