@@ -568,6 +568,113 @@ int rt_features_resolve(const double* sums, int64_t pixels, int n_samples, doubl
                         double* out_depth, double* out_coverage, uint8_t* out_albedo_rgb8);
 
 /*
+ * Feature-guided denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with SVGF-style variance
+ * guidance over a linear image, its per-pixel standard error (optional) and the feature sums of a feature pass
+ * (above). Tier-independent; every array is in image order (row 0 = top). fp64 throughout, no contraction, only
+ * + - * /, sqrt, fabs and comparisons, so that the host function and the device kernels give the same bits; the
+ * falloffs are compact rationals (no exp). One per-pixel text serves both (ray-tracing_amd/csrc/rt_denoise.h).
+ *
+ * Inputs per pixel p of an H x W image: color[p][3] (rt_render's out_linear, rt_frame_resolve's or
+ * rt_checkpoint_resolve's), se[p][3] (rt_frame_error's map; the pointer may be NULL) and feature_sums[p][8] of
+ * n = feature_samples >= 1 samples, exactly as rt_render_features wrote them.
+ *
+ * Guides, computed once: N = normal sum / n (not renormalised); Z = depth sum / hits, or 0.0 where hits == 0
+ * (not rt_features_resolve's +inf); A_c = albedo sum_c / n, and a_c = A_c clamped to [1e-3, 1]:
+ * A_c > 1e-3 ? (A_c < 1.0 ? A_c : 1.0) : 1e-3 (a NaN albedo: 1e-3). The upper bound keeps emitters, whose first-hit
+ * "albedo" is their radiance, and the pixels on their edges in their own units: divided by a radiance they would all
+ * be 1 and take up their darker neighbours, which the multiplication at the end would then scale up.
+ * Variance: V = ((0.2126 e_r)^2 + (0.7152 e_g)^2) + (0.0722 e_b)^2, each term (k * e) * (k * e), with e_c = se_c, or
+ * under RT_DENOISE_DEMODULATE in a valid pixel e_c = se_c / a_c, the standard error of the channel the filter
+ * sees; V = 0.0 when se is NULL, when one of the pixel's three se channels is not finite, or when that sum is not
+ * finite. Luminance L(c) = (0.2126 r + 0.7152 g) + 0.0722 b. "Finite" is |x| <= DBL_MAX. A pixel is valid when its
+ * three colour channels, as its buffer holds them at that moment, are finite.
+ *
+ * Demodulation (RT_DENOISE_DEMODULATE): before the first iteration a valid pixel's colour becomes color_c / a_c;
+ * after the last, a pixel valid then becomes c_c * a_c. An invalid pixel's channels are never touched by either
+ * step (they are copied, bit for bit).
+ *
+ * Iteration i = 0 .. iterations - 1 (1..8) has stride s = 2^i and maps one buffer of (colour, V) per pixel to the
+ * next (two buffers, ping-pong). For centre p = (x, y), the 25 taps are q = (x + s dx, y + s dy), dy outer and dx
+ * inner, both from -2 to 2: this is the order of every sum below. A tap outside the image or invalid is skipped.
+ * Per centre, one division each: rz = 1 / (sigma_depth * Z_p + 1e-12), rc = 1 / (sigma_color * sqrt(V_p) +
+ * color_floor); rn = 1 / (sigma_normal * sigma_normal) is computed once per call on the host. With
+ * f(x) = x < 1.0 ? (1 - x) * (1 - x) : 0.0 (a NaN x gives 0) and k = {3/8, 1/4, 1/16}, a tap's weight is
+ *     w = ((h * w_n) * w_z) * w_c,     h = k[|dx|] * k[|dy|],
+ *     w_n = f((((N_p - N_q)_x^2 + (N_p - N_q)_y^2) + (N_p - N_q)_z^2) * rn),
+ *     w_z = f(|Z_p - Z_q| * rz),       w_c = f(|L(c_p) - L(c_q)| * rc),
+ * w_c = 1.0 under RT_DENOISE_GUIDES_ONLY. The sums start at 0: acc_c += w * c_q (multiply, then add),
+ * wsum += w, vacc += (w * w) * V_q. If wsum > 0 the pixel becomes c' = acc / wsum, V' = vacc / (wsum * wsum); if
+ * not (no tap has weight, or a NaN) the pixel's four values pass through unchanged.
+ * An invalid centre passes through unchanged (a NaN frame's NaN pixels stay NaN, bit for bit, and change no
+ * neighbour, being skipped as taps), unless RT_DENOISE_FILL is set: then it runs the same sums with w_c = 1.0, and
+ * with wsum > 0 it takes c' and V' and is valid from the next iteration on.
+ *
+ * Outputs: out_color[p][3]; out_rgb8 (optional) = out_color through scaleColor, as rt_features_resolve's albedo
+ * bytes (NaN -> 0). Stats: pixels = H*W; invalid_in = pixels of `color` with a channel that is not finite;
+ * invalid_out = the same count over out_color; filled = pixels invalid in `color` and valid in out_color; all
+ * exact. kernel_ms = HIP-event time of the call's kernels (0 from the host function).
+ *
+ * rt_denoise_host   host only, no device: the definition, and the offline half of a checkpoint workflow
+ *                   (rt_checkpoint_resolve's linear image, rt_checkpoint_error's map). se, out_rgb8 and stats may be
+ *                   NULL. out_color must not overlap an input.
+ * rt_denoise        the same on the ctx's device (a multi-device ctx: its first), host pointers, blocking; bit for
+ *                   bit rt_denoise_host's outputs and counts. Needs a ctx but no scene.
+ * rt_denoise_async  the kernels queued on `stream` over device pointers in image order (d_se and d_out_rgb8 may be
+ *                   NULL); composes with rt_render_features_async. The inputs are read until the last kernel ends.
+ * rt_frame_denoise  an unsharded frame's current preview (rt_frame_resolve's S / N_p), with its rt_frame_error map
+ *                   when the frame tracks moments and chunks_done >= 2 (else no se), denoised on the device against
+ *                   d_feature_sums (device memory, [H][W][8], e.g. rt_render_features_async's); only the result is
+ *                   copied back (out_rgb8, out_linear, stats: each may be NULL). params->width and height must be
+ *                   the frame's. The frame's sums, its stored preview and its bytes_changed accounting are left
+ *                   alone. RT_E_STATE: no scene, no chunk rendered, or a shard frame (a sharded denoise needs a halo
+ *                   exchange between the shards, which is not covered).
+ * rt_last_denoise   of the ctx's last denoise call: device_allocs = device allocations it made (the ctx keeps the
+ *                   guide records, the two (colour, V) buffers and its staging buffers and grows them on demand, so
+ *                   a repeat of one image size makes none); launches = kernels queued (iterations + 2); lds_bytes =
+ *                   the iteration kernel's LDS per workgroup.
+ * RT_E_INVALID, before any HIP call: a null required pointer; width or height < 1; iterations outside 1..8;
+ * feature_samples < 1; unknown flag bits; sigma_color, sigma_normal, sigma_depth or color_floor not > 0 or not
+ * finite; an image of 2^31 pixels or more. The kernels are ordered after the ctx's previous tier-B launch and
+ * before its next, whichever streams they use; a denoise between two renders leaves the renders' bytes unchanged.
+ */
+#define RT_DENOISE_DEMODULATE 1u  /* filter colour / albedo, multiply the albedo back at the end */
+#define RT_DENOISE_GUIDES_ONLY 2u /* w_c = 1: normal and depth weights only */
+#define RT_DENOISE_FILL 4u        /* replace invalid (NaN, infinite) pixels by their valid neighbourhood */
+#define RT_DENOISE_MAX_ITERATIONS 8
+typedef struct rt_denoise_params {
+    int32_t width;
+    int32_t height;
+    int32_t iterations;      /* 1..8; iteration i has stride 2^i */
+    int32_t feature_samples; /* n of feature_sums */
+    uint32_t flags;          /* RT_DENOISE_* */
+    int32_t _pad;
+    double sigma_color;  /* in standard errors of the centre's luminance */
+    double color_floor;  /* added to sigma_color * sqrt(V_p): the luminance scale where V is 0 */
+    double sigma_normal; /* |N_p - N_q| at which w_n reaches 0 */
+    double sigma_depth;  /* |Z_p - Z_q| / Z_p at which w_z reaches 0 */
+} rt_denoise_params; /* 56 bytes */
+typedef struct rt_denoise_stats {
+    int64_t pixels;
+    int64_t invalid_in;
+    int64_t invalid_out;
+    int64_t filled;
+    double kernel_ms;
+} rt_denoise_stats; /* 40 bytes */
+typedef struct rt_denoise_info {
+    int32_t device_allocs;
+    int32_t launches;
+    int32_t lds_bytes;
+    int32_t _pad;
+} rt_denoise_info; /* 16 bytes */
+int rt_denoise_host(const rt_denoise_params* params, const double* color, const double* se,
+                    const double* feature_sums, double* out_color, uint8_t* out_rgb8, rt_denoise_stats* stats);
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, const double* color, const double* se,
+               const double* feature_sums, double* out_color, uint8_t* out_rgb8, rt_denoise_stats* stats);
+int rt_denoise_async(rt_ctx* ctx, const rt_denoise_params* params, const double* d_color, const double* d_se,
+                     const double* d_feature_sums, double* d_out_color, uint8_t* d_out_rgb8, void* stream);
+int rt_last_denoise(rt_ctx* ctx, rt_denoise_info* out);
+
+/*
  * Progressive tier-B frames: the image of rt_render, rendered a few sample chunks at a time.
  * A frame holds the running per-pixel sums of the chunks rendered so far (RT_RNG_PHILOX above: chunk
  * sums added in chunk order from 0), so that a caller can look at the image while it converges, stop
@@ -935,6 +1042,9 @@ int rt_scene_fingerprint(const rt_scene_desc* desc, uint64_t* out);
  * rt_sample_chunk(pixels, spp), *out_chunks_total = ceil(spp / chunk). For callers that cannot use the
  * header's inline (other languages): one rule, this header's. */
 int rt_frame_chunking(int64_t pixels, int spp, int* out_chunk, int* out_chunks_total);
+/* The denoised preview of an unsharded frame (the feature-guided denoiser, above). */
+int rt_frame_denoise(rt_frame* f, const rt_denoise_params* params, const double* d_feature_sums, uint8_t* out_rgb8,
+                     double* out_linear, rt_denoise_stats* stats);
 
 /*
  * Debug / parity entry: closest hit of n world rays (7 doubles each: origin, direction, time)

@@ -4,17 +4,8 @@
 #include <limits>
 
 #include "rt.h"
+#include "rt_denoise.h"  // (scale_color8: scaleColor, shared with the denoiser's outputs)
 #include "rt_internal.h"
-
-namespace {
-// scaleColor (Lib.hs:287-288) as the device's scale_color (rt_kernels.h): NaN -> 0, +inf -> 255.
-uint8_t scale_color(double x) {
-  const double s = std::sqrt(x);
-  const double cl = s < 0.0 ? 0.0 : (s > 0.999 ? 0.999 : s);
-  const double f = std::floor(256 * cl);
-  return f == f ? (uint8_t)(int)f : (uint8_t)0;
-}
-}  // namespace
 
 extern "C" int rt_features_resolve(const double* sums, int64_t pixels, int n_samples, double* out_albedo,
                                    double* out_normal, double* out_depth, double* out_coverage,
@@ -29,7 +20,7 @@ extern "C" int rt_features_resolve(const double* sums, int64_t pixels, int n_sam
     for (int c = 0; c < 3; ++c) {
       const double a = s[RT_FEAT_ALBEDO + c] / n;
       if (out_albedo) out_albedo[3 * i + c] = a;
-      if (out_albedo_rgb8) out_albedo_rgb8[3 * i + c] = scale_color(a);
+      if (out_albedo_rgb8) out_albedo_rgb8[3 * i + c] = rt::scale_color8(a);
       if (out_normal) out_normal[3 * i + c] = s[RT_FEAT_NORMAL + c] / n;
     }
     const double hits = s[RT_FEAT_HITS];

@@ -1,7 +1,8 @@
 // rt_render.hip — the device half of the C ABI (include/rt.h): scene upload, launches, assembly,
 // debug probes. The render kernels are templates in rt_kernels.h, instantiated per scene variant in
 // rt_k_spheres.hip / rt_k_cornell.hip / rt_k_full.hip / rt_k_full_dark.hip; the first-hit feature pass's
-// (rt_render_features) in rt_k_features.hip.
+// (rt_render_features) in rt_k_features.hip; the denoiser's (rt_denoise*) with their launch sequence in
+// rt_k_denoise.hip.
 //
 // Kernel design:
 //  * tier B work-items are (pixel, chunk of up to 32 samples): a lane sums its chunk in sample
@@ -29,6 +30,7 @@
 #include <numeric>
 #include <vector>
 
+#include "rt_denoise.h"
 #include "rt_frame_blob.h"
 #include "rt_kernels.h"
 #include "rt_prepare.h"
@@ -83,6 +85,12 @@ struct rt_ctx {
   // colours (LaunchConst::tail_buf), the running per-pixel sums of a frame rendered in chunk batches
   FrameBuf fb_partial, fb_tail, fb_acc;
   int allocs = 0;  // hipMalloc calls made on this device by the current rt_render (rt_frame_timing)
+  // The denoiser's buffers (rt.h rt_denoise*), kept and grown like the frame buffers: the guide records and the two
+  // (colour, V) buffers, its counts; the device copies of a blocking call's inputs and outputs (rt_frame_denoise:
+  // the frame's preview and error map), and the scratch counts of that preview's frame_resolve launch
+  FrameBuf dn_guide, dn_a, dn_b, dn_counts, dn_color, dn_se, dn_feat, dn_out, dn_rgb, dn_fcounts;
+  hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;  // around a blocking denoise call's kernels (kernel_ms)
+  rt_denoise_info last_denoise{};                 // rt_last_denoise
   // Progressive frames open on this ctx (rt_frame_*), and what a saved frame records of the scene: the
   // fingerprint of the caller's descriptor and the upload flags (rt_frame_blob.cpp)
   std::vector<rt_frame*> frames;
@@ -213,7 +221,9 @@ int grow(rt_ctx* c, rt_ctx::FrameBuf& b, size_t need) {
 }
 void free_frame_bufs(rt_ctx* c) {
   for (rt_ctx::FrameBuf* b : {&c->fb_slab, &c->fb_slab_lin, &c->fb_gather, &c->fb_gather_lin, &c->fb_img,
-                              &c->fb_img_lin, &c->fb_gens, &c->fb_partial, &c->fb_tail, &c->fb_acc}) {
+                              &c->fb_img_lin, &c->fb_gens, &c->fb_partial, &c->fb_tail, &c->fb_acc, &c->dn_guide,
+                              &c->dn_a, &c->dn_b, &c->dn_counts, &c->dn_color, &c->dn_se, &c->dn_feat, &c->dn_out,
+                              &c->dn_rgb, &c->dn_fcounts}) {
     (void)hipFree(b->p);
     b->p = nullptr;
     b->bytes = 0;
@@ -581,6 +591,8 @@ int rt_create(int device, rt_ctx** out) {
     HIPCHK(hipEventCreate(&c->ev_gather));
     HIPCHK(hipEventCreate(&c->ev_gathered));
     HIPCHK(hipEventCreate(&c->ev_asm));
+    HIPCHK(hipEventCreate(&c->ev_dn0));
+    HIPCHK(hipEventCreate(&c->ev_dn1));
     HIPCHK(hipMalloc((void**)&c->d_counter, kCounterBytes + sizeof(LaunchConst)));
     return RT_OK;
   };
@@ -667,6 +679,8 @@ void rt_destroy(rt_ctx* c) {
   if (c->ev_gather) (void)hipEventDestroy(c->ev_gather);
   if (c->ev_gathered) (void)hipEventDestroy(c->ev_gathered);
   if (c->ev_asm) (void)hipEventDestroy(c->ev_asm);
+  if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
+  if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1861,6 +1875,144 @@ void rt_frame_close(rt_frame* f) {
   (void)hipStreamSynchronize(c->stream);  // (its queued launches write its buffers)
   c->frames.erase(std::remove(c->frames.begin(), c->frames.end(), f), c->frames.end());
   frame_free(f);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ feature-guided denoiser (rt.h)
+namespace {
+
+// rt_denoise*'s argument checks (rt.h), before any HIP call; the ctx last, as features_check.
+int denoise_check(const char* what, const rt_ctx* c, const rt_denoise_params* p, bool pointers) {
+  const char* bad = rt::denoise_params_error(p);
+  if (!bad && !pointers) bad = "null color, feature_sums or out_color";
+  if (!bad && !c) bad = "null ctx";
+  return bad ? invalid(std::string(what) + ": " + bad) : RT_OK;
+}
+
+// The kernels of one denoise call queued on `st` over device pointers (the ctx's device is selected), in the ctx's
+// own buffers, grown on demand. Like a feature pass it takes its place in the ctx's launch order: after the
+// previous launch (ev_done), and the next one, which may be another denoise in the same buffers, waits for it.
+// `timed`: the ctx's ev_dn0 / ev_dn1 are recorded around the kernels.
+int denoise_queue(rt_ctx* c, const rt_denoise_params* p, const double* d_color, const double* d_se,
+                  const double* d_feat, double* d_out, uint8_t* d_rgb, hipStream_t st, bool timed) {
+  const size_t npx = (size_t)p->width * (size_t)p->height;
+  int rc;
+  if ((rc = grow(c, c->dn_guide, 32 * npx)) || (rc = grow(c, c->dn_a, 32 * npx)) || (rc = grow(c, c->dn_b, 32 * npx)) ||
+      (rc = grow(c, c->dn_counts, 3 * sizeof(unsigned long long))))
+    return rc;
+  if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
+  c->last_stream = st;
+  if (timed) HIPCHK(hipEventRecord(c->ev_dn0, st));
+  const rt::DenoiseBuffers B{c->dn_guide.p, c->dn_a.p, c->dn_b.p, (unsigned long long*)c->dn_counts.p};
+  int launches = 0;
+  const int e = rt::denoise_launch(rt::denoise_const(*p), p->iterations, d_color, d_se, d_feat, B, d_out, d_rgb,
+                                   (void*)st, &launches);
+  if (e) return hip_fail((hipError_t)e, "rt_denoise launch");
+  if (timed) HIPCHK(hipEventRecord(c->ev_dn1, st));
+  HIPCHK(hipEventRecord(c->ev_done, st));
+  c->last_denoise = rt_denoise_info{c->allocs, launches, (int32_t)rt::kDenoiseLdsBytes, 0};
+  return RT_OK;
+}
+
+// A blocking call's kernels on the ctx's stream, then its stats (may be null) from the device's counts.
+int denoise_run(rt_ctx* c, const rt_denoise_params* p, const double* d_color, const double* d_se, const double* d_feat,
+                double* d_out, uint8_t* d_rgb, rt_denoise_stats* stats) {
+  int rc = denoise_queue(c, p, d_color, d_se, d_feat, d_out, d_rgb, c->stream, true);
+  unsigned long long counts[3] = {0, 0, 0};
+  if (!rc) rc = hip_ok(hipMemcpyAsync(counts, c->dn_counts.p, sizeof counts, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (rc) return rc;
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_dn0, c->ev_dn1));
+    stats->pixels = (int64_t)p->width * p->height;
+    stats->invalid_in = (int64_t)counts[0];
+    stats->invalid_out = (int64_t)counts[1];
+    stats->filled = (int64_t)counts[2];
+    stats->kernel_ms = ms;
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_denoise_async(rt_ctx* c, const rt_denoise_params* p, const double* d_color, const double* d_se,
+                     const double* d_feature_sums, double* d_out_color, uint8_t* d_out_rgb8, void* stream) {
+  int rc = denoise_check("rt_denoise_async", c, p, d_color && d_feature_sums && d_out_color);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  return denoise_queue(c, p, d_color, d_se, d_feature_sums, d_out_color, d_out_rgb8, (hipStream_t)stream, false);
+}
+
+int rt_denoise(rt_ctx* c, const rt_denoise_params* p, const double* color, const double* se, const double* feature_sums,
+               double* out_color, uint8_t* out_rgb8, rt_denoise_stats* stats) {
+  int rc = denoise_check("rt_denoise", c, p, color && feature_sums && out_color);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  const size_t npx = (size_t)p->width * (size_t)p->height, img = sizeof(double) * 3 * npx;
+  if ((rc = grow(c, c->dn_color, img)) || (se && (rc = grow(c, c->dn_se, img))) ||
+      (rc = grow(c, c->dn_feat, sizeof(double) * RT_FEATURE_DOUBLES * npx)) || (rc = grow(c, c->dn_out, img)) ||
+      (out_rgb8 && (rc = grow(c, c->dn_rgb, 3 * npx))))
+    return rc;
+  HIPCHK(hipMemcpy(c->dn_color.p, color, img, hipMemcpyHostToDevice));
+  if (se) HIPCHK(hipMemcpy(c->dn_se.p, se, img, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->dn_feat.p, feature_sums, sizeof(double) * RT_FEATURE_DOUBLES * npx, hipMemcpyHostToDevice));
+  if ((rc = denoise_run(c, p, (const double*)c->dn_color.p, se ? (const double*)c->dn_se.p : nullptr,
+                        (const double*)c->dn_feat.p, (double*)c->dn_out.p, out_rgb8 ? (uint8_t*)c->dn_rgb.p : nullptr,
+                        stats)))
+    return rc;
+  HIPCHK(hipMemcpy(out_color, c->dn_out.p, img, hipMemcpyDeviceToHost));
+  if (out_rgb8) HIPCHK(hipMemcpy(out_rgb8, c->dn_rgb.p, 3 * npx, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_last_denoise(rt_ctx* c, rt_denoise_info* out) {
+  if (!c || !out) return invalid("null argument");
+  *out = c->last_denoise;
+  return RT_OK;
+}
+
+int rt_frame_denoise(rt_frame* f, const rt_denoise_params* p, const double* d_feature_sums, uint8_t* out_rgb8,
+                     double* out_linear, rt_denoise_stats* stats) {
+  if (!f) return invalid("rt_frame_denoise: null frame");
+  rt_ctx* c = f->ctx;
+  int rc = denoise_check("rt_frame_denoise", c, p, d_feature_sums != nullptr);
+  if (rc) return rc;
+  if (p->width != f->p.width || p->height != f->p.height)
+    return invalid("rt_frame_denoise: params->width and height must be the frame's");
+  if ((rc = frame_live(f, "rt_frame_denoise"))) return rc;
+  if (f->shard)
+    return state_error("rt_frame_denoise: a shard frame cannot be denoised (a tap may lie in another shard's slab: a "
+                       "sharded denoise needs a halo exchange); assemble the shards' previews and call rt_denoise_async");
+  if (f->chunks_done == 0) return state_error("rt_frame_denoise: no chunk rendered yet");
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  const size_t npx = (size_t)f->npx, img = sizeof(double) * 3 * npx;
+  const bool with_se = f->d_q && f->chunks_done >= 2;
+  if ((rc = grow(c, c->dn_color, img)) || (with_se && (rc = grow(c, c->dn_se, img))) || (rc = grow(c, c->dn_out, img)) ||
+      (rc = grow(c, c->dn_rgb, 3 * npx)) || (rc = grow(c, c->dn_fcounts, 2 * sizeof(unsigned long long))))
+    return rc;
+  // The preview, by rt_frame_resolve's kernel into the ctx's buffers: the frame's own preview, the bytes it
+  // compares the next resolve with and its counts stay as they are (the scratch bytes are then the denoised ones).
+  LaunchConst A{};
+  frame_const(f, A);
+  A.out_rgb = (uint8_t*)c->dn_rgb.p;
+  A.out_lin = (double*)c->dn_color.p;
+  HIPCHK(hipMemsetAsync(c->dn_fcounts.p, 0, 2 * sizeof(unsigned long long), c->stream));
+  FRAME_KERNEL_ADAPT(f, frame_resolve, A, frame_samples(f), (unsigned long long*)c->dn_fcounts.p, (const int*)f->d_kp);
+  HIPCHK(hipGetLastError());
+  if (with_se && (rc = frame_error_run(f, 0.0, 0.0, (double*)c->dn_se.p, f->npx, nullptr))) return rc;
+  if ((rc = denoise_run(c, p, (const double*)c->dn_color.p, with_se ? (const double*)c->dn_se.p : nullptr, d_feature_sums,
+                        (double*)c->dn_out.p, out_rgb8 ? (uint8_t*)c->dn_rgb.p : nullptr, stats)))
+    return rc;
+  if (out_linear) HIPCHK(hipMemcpy(out_linear, c->dn_out.p, img, hipMemcpyDeviceToHost));
+  if (out_rgb8) HIPCHK(hipMemcpy(out_rgb8, c->dn_rgb.p, 3 * npx, hipMemcpyDeviceToHost));
+  return RT_OK;
 }
 
 int rt_debug_closest_hits(rt_ctx* c, const double* rays, int n, double tmin, double tmax, uint64_t seed,

@@ -169,6 +169,23 @@ class rt_frame_ckpt_desc(C.Structure):
                 ("stopped_pixels", C.c_int64), ("stopped_nan", C.c_int64), ("active_pixels", C.c_int64)]
 
 
+class rt_denoise_params(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("feature_samples", C.c_int32), ("flags", C.c_uint32), ("_pad", C.c_int32),
+                ("sigma_color", C.c_double), ("color_floor", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double)]
+
+
+class rt_denoise_stats(C.Structure):
+    _fields_ = [("pixels", C.c_int64), ("invalid_in", C.c_int64), ("invalid_out", C.c_int64), ("filled", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
+class rt_denoise_info(C.Structure):
+    _fields_ = [("device_allocs", C.c_int32), ("launches", C.c_int32), ("lds_bytes", C.c_int32), ("_pad", C.c_int32)]
+
+
+assert C.sizeof(rt_denoise_params) == 56 and C.sizeof(rt_denoise_stats) == 40 and C.sizeof(rt_denoise_info) == 16
 assert C.sizeof(rt_frame_ckpt_desc) == 344
 assert C.sizeof(rt_error_tol) == 16 and C.sizeof(rt_error_stats) == 48
 assert C.sizeof(rt_adapt_rule) == 24 and C.sizeof(rt_adapt_stats) == 48
@@ -199,7 +216,14 @@ EXPORTED = [
     "rt_frame_checkpoint_info", "rt_checkpoint_resolve", "rt_checkpoint_error", "rt_frame_checkpoint",
     "rt_frame_resume", "rt_frame_resume_shard", "rt_frame_shard_stops", "rt_frame_checkpoint_header",
     "rt_render_features", "rt_render_features_async", "rt_last_feature_launch", "rt_features_resolve",
+    "rt_denoise_host", "rt_denoise", "rt_denoise_async", "rt_last_denoise", "rt_frame_denoise",
 ]
+
+# The feature-guided denoiser's flags (rt.h)
+RT_DENOISE_DEMODULATE = 1   # filter colour / albedo, multiply the albedo back at the end
+RT_DENOISE_GUIDES_ONLY = 2  # normal and depth weights only (no colour weight)
+RT_DENOISE_FILL = 4         # replace invalid (NaN, infinite) pixels by their valid neighbourhood
+RT_DENOISE_MAX_ITERATIONS = 8
 
 # First-hit feature buffers (rt.h): doubles per pixel of a feature pass's sums, and where each feature starts
 RT_FEATURE_DOUBLES, RT_FEAT_ALBEDO, RT_FEAT_NORMAL, RT_FEAT_DEPTH, RT_FEAT_HITS = 8, 0, 3, 6, 7
@@ -330,6 +354,16 @@ def lib() -> C.CDLL:
                                              C.c_void_p]),
             "rt_last_feature_launch": (I, [C.c_void_p, P(rt_launch_info)]),
             "rt_features_resolve": (I, [P(D), C.c_int64, I, P(D), P(D), P(D), P(D), P(C.c_uint8)]),
+            "rt_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8), P(rt_denoise_stats)]),
+            "rt_internal_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8),
+                                             P(rt_denoise_stats), P(D)]),
+            "rt_denoise": (I, [C.c_void_p, P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8),
+                               P(rt_denoise_stats)]),
+            "rt_denoise_async": (I, [C.c_void_p, P(rt_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+            "rt_last_denoise": (I, [C.c_void_p, P(rt_denoise_info)]),
+            "rt_frame_denoise": (I, [C.c_void_p, P(rt_denoise_params), C.c_void_p, P(C.c_uint8), P(D),
+                                     P(rt_denoise_stats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -820,6 +854,25 @@ class Context:
         _check(lib().rt_last_feature_launch(self._h, C.byref(info)), "rt_last_feature_launch")
         return {k: getattr(info, k) for k, _ in rt_launch_info._fields_}
 
+    def denoise(self, params: "rt_denoise_params", color, se, feature_sums, rgb: bool = True):
+        """rt_denoise: `denoise_host` on this ctx's device, bit for bit; host arrays, blocking. Needs no scene."""
+        return _denoise_call(lib().rt_denoise, "rt_denoise", (self._h,), params, color, se, feature_sums, rgb)
+
+    def denoise_async(self, params: "rt_denoise_params", d_color: int, d_se: int, d_feature_sums: int,
+                      d_out_color: int, d_out_rgb8: int = 0, stream: int = 0):
+        """rt_denoise_async: the denoiser's kernels queued on `stream` over device pointers in image order (d_se and
+        d_out_rgb8 may be 0); composes with `render_features_async`."""
+        _check(lib().rt_denoise_async(self._h, C.byref(params), C.c_void_p(d_color), C.c_void_p(d_se or None),
+                                      C.c_void_p(d_feature_sums), C.c_void_p(d_out_color),
+                                      C.c_void_p(d_out_rgb8 or None), C.c_void_p(stream or None)), "rt_denoise_async")
+
+    def last_denoise(self) -> dict:
+        """rt_last_denoise: device allocations of the ctx's last denoise call (0 on a repeat of one image size), the
+        kernels it queued, the iteration kernel's LDS bytes per workgroup."""
+        info = rt_denoise_info()
+        _check(lib().rt_last_denoise(self._h, C.byref(info)), "rt_last_denoise")
+        return {"device_allocs": info.device_allocs, "launches": info.launches, "lds_bytes": info.lds_bytes}
+
     def wide_keys(self) -> dict:
         """rt_debug_wide_keys: whether the last 4-wide walk sorted packed keys, whether the uploaded world is
         within their id bound, the reference bits of a packed word, the most 4-wide nodes LDS staging holds."""
@@ -893,6 +946,80 @@ def resolve_features(sums: np.ndarray, n_samples: int) -> dict:
                                      out["coverage"].ctypes.data_as(P(C.c_double)),
                                      out["albedo_rgb8"].ctypes.data_as(P(C.c_uint8))), "rt_features_resolve")
     return out
+
+
+DENOISE_STATS_FIELDS = ("pixels", "invalid_in", "invalid_out", "filled", "kernel_ms")
+
+
+def make_denoise_params(width: int, height: int, feature_samples: int, iterations: int = 5, flags: int = 0,
+                        sigma_color: float = 4.0, color_floor: float = 0.05, sigma_normal: float = 0.5,
+                        sigma_depth: float = 0.2) -> rt_denoise_params:
+    """rt_denoise_params (rt.h) with the documented defaults: 5 a-trous iterations (strides 1..16, a 65-pixel
+    footprint); sigma_color = 4: a tap's colour weight reaches 0 at 4 standard errors of the centre's luminance, plus
+    color_floor = 0.05, the luminance scale where no error estimate is given or it is 0 (raise it for a frame
+    without moments, whose filter is otherwise guided by normal and depth alone); sigma_normal = 0.5: the normal
+    weight reaches 0 where the first-hit normals differ by 0.5 (about 29 degrees); sigma_depth = 0.2: the depth
+    weight reaches 0 at a 20 % difference from the centre's first-hit depth. flags: RT_DENOISE_DEMODULATE |
+    RT_DENOISE_GUIDES_ONLY | RT_DENOISE_FILL."""
+    p = rt_denoise_params()
+    p.width, p.height, p.iterations, p.feature_samples, p.flags = width, height, iterations, feature_samples, flags
+    p.sigma_color, p.color_floor, p.sigma_normal, p.sigma_depth = sigma_color, color_floor, sigma_normal, sigma_depth
+    return p
+
+
+def _denoise_inputs(params: rt_denoise_params, color, se, feature_sums):
+    """A denoise call's host arrays, checked against the params' image: colour and se (H, W, 3), feature sums
+    (H, W, 8), float64 in C order."""
+    H, W = params.height, params.width
+    arrays = []
+    for name, a, ch in (("color", color, 3), ("se", se, 3), ("feature_sums", feature_sums, RT_FEATURE_DOUBLES)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (H, W, ch):
+                raise RTError(f"denoise: `{name}` must have shape {(H, W, ch)}, got {a.shape}")
+        elif name != "se":
+            raise RTError(f"denoise: `{name}` is required")
+        arrays.append(a)
+    return arrays
+
+
+def _denoise_stats_dict(s: rt_denoise_stats) -> dict:
+    return {k: getattr(s, k) for k in DENOISE_STATS_FIELDS}
+
+
+def _denoise_call(fn, what: str, head: tuple, params: rt_denoise_params, color, se, feature_sums, rgb: bool):
+    P = C.POINTER
+    color, se, feature_sums = _denoise_inputs(params, color, se, feature_sums)
+    out = np.zeros((params.height, params.width, 3), dtype=np.float64)
+    out_rgb = np.zeros((params.height, params.width, 3), dtype=np.uint8) if rgb else None
+    s = rt_denoise_stats()
+    _check(fn(*head, C.byref(params), color.ctypes.data_as(P(C.c_double)),
+              se.ctypes.data_as(P(C.c_double)) if se is not None else None,
+              feature_sums.ctypes.data_as(P(C.c_double)), out.ctypes.data_as(P(C.c_double)),
+              out_rgb.ctypes.data_as(P(C.c_uint8)) if rgb else None, C.byref(s)), what)
+    return out_rgb, out, _denoise_stats_dict(s)
+
+
+def denoise_host(params: rt_denoise_params, color, se, feature_sums, rgb: bool = True):
+    """rt_denoise_host: the feature-guided denoiser (rt.h) on the host, no device: (rgb8[H,W,3] | None,
+    linear[H,W,3], stats dict) of a linear image, its standard-error map (or None) and a feature pass's sums. The
+    definition `Context.denoise` is compared with, and the filter of a checkpoint's preview (`checkpoint_resolve`,
+    `checkpoint_error`)."""
+    return _denoise_call(lib().rt_denoise_host, "rt_denoise_host", (), params, color, se, feature_sums, rgb)
+
+
+def denoise_host_variance(params: rt_denoise_params, color, se, feature_sums) -> Tuple[np.ndarray, np.ndarray]:
+    """(linear[H,W,3], variance[H,W]) of `denoise_host`: its image and, for tests of the definition, the filtered
+    luminance variance V of every pixel after the last iteration (the library's internal entry; not in rt.h)."""
+    P = C.POINTER
+    color, se, feature_sums = _denoise_inputs(params, color, se, feature_sums)
+    out = np.zeros((params.height, params.width, 3), dtype=np.float64)
+    var = np.zeros((params.height, params.width), dtype=np.float64)
+    _check(lib().rt_internal_denoise_host(C.byref(params), color.ctypes.data_as(P(C.c_double)),
+                                          se.ctypes.data_as(P(C.c_double)) if se is not None else None,
+                                          feature_sums.ctypes.data_as(P(C.c_double)), out.ctypes.data_as(P(C.c_double)),
+                                          None, None, var.ctypes.data_as(P(C.c_double))), "rt_denoise_host")
+    return out, var
 
 
 def shard_geometry(params: rt_render_params) -> Tuple[int, int, int]:

@@ -199,6 +199,29 @@ class ProgressiveFrame:
                    "rt_frame_chunk_counts")
         return k
 
+    def denoise(self, feature_sums, feature_samples: int, rgb: bool = True, linear: bool = True, **params):
+        """rt_frame_denoise: (rgb8[H,W,3] | None, linear[H,W,3] | None, stats dict) of the frame's current preview
+        through the feature-guided denoiser (rt.h), on the device: the preview is `resolve`'s, its error map
+        `error`'s when the frame tracks moments and has two chunks (else none), and only the result is copied
+        back. `feature_sums`: a feature pass's sums of `feature_samples` samples, [H, W, 8], as a torch tensor on
+        the frame's device (e.g. what `Context.render_features_async` filled), a device address, or a numpy array
+        (copied to the device through torch). `params`: `rtamd.make_denoise_params`' keywords (iterations, flags,
+        sigma_color, color_floor, sigma_normal, sigma_depth). The frame itself is left as it is: its next
+        `resolve` reports the bytes_changed it would have reported. RTError (RT_E_STATE) on a shard frame."""
+        p = _rt.make_denoise_params(self.width, self.height, int(feature_samples), **params)
+        if isinstance(feature_sums, np.ndarray):
+            import torch
+            feature_sums = torch.from_numpy(_doubles(feature_sums, (self.height, self.width, _rt.RT_FEATURE_DOUBLES))
+                                            ).to(f"cuda:{self._ctx.device}")
+        out_rgb = np.zeros((self.height, self.width, 3), dtype=np.uint8) if rgb else None
+        out_lin = np.zeros((self.height, self.width, 3), dtype=np.float64) if linear else None
+        s = _rt.rt_denoise_stats()
+        P = C.POINTER
+        _rt._check(_rt.lib().rt_frame_denoise(
+            self._handle(), C.byref(p), _dev_ptr(feature_sums), out_rgb.ctypes.data_as(P(C.c_uint8)) if rgb else None,
+            out_lin.ctypes.data_as(P(C.c_double)) if linear else None, C.byref(s)), "rt_frame_denoise")
+        return out_rgb, out_lin, _rt._denoise_stats_dict(s)
+
     def close(self):
         # (rt_destroy closes the ctx's open frames itself: after Context.close the handle is dead)
         if self._h is not None and self._ctx._h is not None:
