@@ -568,6 +568,65 @@ int rt_features_resolve(const double* sums, int64_t pixels, int n_samples, doubl
                         double* out_depth, double* out_coverage, uint8_t* out_albedo_rgb8);
 
 /*
+ * Specular-chain feature buffers: the same guides seen through glass and in mirrors. A first-hit pass gives a glass
+ * ball the albedo (1,1,1) and a mirror its own texture, with the sphere's normal and depth: smooth guides over
+ * everything seen in or through the ball. A chain pass follows the sample's path through specular scatters and takes
+ * the features at the first vertex that is not followed, the albedo multiplied by the attenuations on the way and
+ * the depth measured as path length. The chain is the exact prefix of the path rt_render traces for that sample.
+ *
+ * Definition. The sample's stream, UV pair and getRay are the first-hit pass's (above). Start with thr = (1,1,1),
+ * len = 0.0, b = 0 and ray = the primary ray, then repeat:
+ *   1. the closest hit of `ray` in [kEps, +inf) exactly as the render's segment takes it: the same tie rule, the
+ *      same keyed ConstantMedium draw at the stream position reached, RT_FLAG_REFERENCE_CULL honoured;
+ *   2. a miss: the vector is (thr * background, 0,0,0, 0, 0), one multiplication per channel (vmul); the sample ends;
+ *   3. len = len + t * sqrt(dot(d, d)) of this segment (the project's dot order, no contraction);
+ *   4. the hit's material is followed when b < max_bounces and it is a Dielectric with RT_CHAIN_DIELECTRIC set, or
+ *      a Metal with RT_CHAIN_METAL set and fuzz <= max_fuzz;
+ *   5. not followed: a = the first-hit rule's albedo of this hit (textureValue for Lambertian, Metal, DiffuseLight on
+ *      either face and Isotropic, (1,1,1) for Dielectric); the vector is (thr * a, n, len, 1.0) with n this hit's
+ *      normal as faceNormal leaves it; the sample ends;
+ *   6. followed: the scattered ray is, bit for bit, the one the render's scatter makes for this hit at this stream
+ *      position: the same draws in the same order (Dielectric one, Metal two even at fuzz 0) and the same
+ *      operations (Metal: reflect(unit(d), n) + fuzz * v as written, at fuzz 0 too: the sign of a zero component can
+ *      differ); thr = thr * attenuation, ray = scattered, ++b.
+ * max_depth is not read. The sums are the first-hit pass's left fold in sample order over the same 8 doubles, so
+ * rt_features_resolve, rt_denoise* and rt_frame_denoise take chain sums unchanged; resolved depth is the mean path
+ * length to the terminal hit. With max_bounces = 0 or flags = 0 every value is the first-hit pass's bit for bit
+ * (1.0 * x is x, and 0.0 + x is x for the positive x a depth is).
+ *
+ * rt_render_features_chain, rt_render_features_chain_async   rt_render_features[_async] with a chain: the same
+ *     contract (ordering through the ctx's tier-B launches, no effect on the renders around it, the first device of
+ *     a multi-device ctx), the same kernel forms, reported by rt_last_feature_launch in the same way. RT_E_INVALID,
+ *     before any HIP call: everything rt_render_features rejects, a null chain, max_bounces outside 0..64, unknown
+ *     flag bits, max_fuzz negative or not finite.
+ * rt_last_feature_chain   the exact counts of the ctx's last chain pass. It waits for that pass first (an event of
+ *     the ctx's own, recorded behind it: the caller's stream need not outlive the call that queued the pass), so
+ *     after an async pass it blocks until the pass has run. RT_E_STATE if no chain pass was made.
+ *     ended_cap / samples tells a caller whether max_bounces is large enough.
+ */
+#define RT_CHAIN_DIELECTRIC 1u
+#define RT_CHAIN_METAL      2u
+#define RT_CHAIN_MAX_BOUNCES 64
+typedef struct rt_feature_chain {
+    int32_t  max_bounces;  /* 0..64: specular scatters followed at most */
+    uint32_t flags;        /* RT_CHAIN_*: which materials are followed */
+    double   max_fuzz;     /* a Metal is followed when its fuzz <= max_fuzz (>= 0, finite) */
+} rt_feature_chain;        /* 16 bytes */
+typedef struct rt_feature_chain_stats {
+    int64_t samples;        /* pixels * n_samples */
+    int64_t ended_surface;  /* terminal hit on a material that is never followed under these flags */
+    int64_t ended_miss;
+    int64_t ended_cap;      /* terminal hit on a material that would have been followed at b < max_bounces */
+    int64_t bounces;        /* specular scatters followed, summed over the samples */
+} rt_feature_chain_stats;   /* 40 bytes */
+int rt_render_features_chain(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                             int first_sample, int n_samples, int accumulate, double* sums);
+int rt_render_features_chain_async(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p,
+                                   const rt_feature_chain* chain, int first_sample, int n_samples, int accumulate,
+                                   double* d_sums, void* stream);
+int rt_last_feature_chain(rt_ctx* ctx, rt_feature_chain_stats* out);
+
+/*
  * Feature-guided denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with SVGF-style variance
  * guidance over a linear image, its per-pixel standard error (optional) and the feature sums of a feature pass
  * (above). Tier-independent; every array is in image order (row 0 = top). fp64 throughout, no contraction, only

@@ -327,6 +327,22 @@ struct RngPhilox {
     philox(c, k0, k1);
     return word_to_draw((uint64_t)c[0] | ((uint64_t)c[1] << 32));
   }
+  // Forget the buffered words and keep the stream position (odd or even): the draws that follow are the same,
+  // their blocks computed again. Never needed for correctness. A register-pressure device, whose effect depends on
+  // where it is called: right after a long walk and before the next draw, the compiler sees the buffer (w0..w3,
+  // 8 VGPRs; the zeroing below is there for that liveness alone) as dead across the walk. `pair` and `n` stay live
+  // wherever the walk reads consumed() for a keyed medium draw (the mixed and recursive forms).
+  __device__ __forceinline__ void rewind() {
+    const uint32_t pos = consumed();
+    pair = pos >> 1;
+    n = 0;
+    w0 = w1 = w2 = w3 = 0;
+    if (pos & 1u) {  // (the position is the second word of its block)
+      uint64_t x;
+      block(x, w0);
+      n = 1;
+    }
+  }
   __device__ __forceinline__ double draw() {
     if (n == 0) block(w0, w1), n = 2;  // not reserved: compute here
     const uint64_t w = w0;

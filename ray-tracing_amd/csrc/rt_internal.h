@@ -86,6 +86,11 @@ extern "C" int rt_internal_launch_plan(const rt_scene_desc* desc, uint32_t uploa
 extern "C" int rt_internal_features_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count,
                                          const rt_render_params* p, rt_launch_info* out, int32_t* out_extra);
 
+// The same for a specular-chain pass (rt_render_features_chain): RT_E_INVALID for a chain the pass rejects.
+extern "C" int rt_internal_features_chain_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count,
+                                               const rt_render_params* p, const rt_feature_chain* chain,
+                                               rt_launch_info* out, int32_t* out_extra);
+
 // rt_denoise_host (rt.h) with one more output for the tests: out_variance (may be null) = V of every pixel after
 // the last iteration, W*H doubles in image order, which the ABI keeps to itself.
 extern "C" int rt_internal_denoise_host(const rt_denoise_params* params, const double* color, const double* se,

@@ -1360,34 +1360,165 @@ __global__ void __launch_bounds__(RT_BLOCK) render_features(FeatureArgs A) {
                             &stk_mem[(((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK) + 1) * RT_BLOCK + threadIdx.x]);
 }
 
-// LDS-staged 4-wide walk (spheres-only worlds): the wide nodes, the leaf table (LEAF_LDS, its own instantiation
-// as in render_philox2_lds) and the lane stacks, `stack_entries` per lane, copied once per workgroup of up to 16
-// waves; the block size is the launch's (1 to 4 waves per SIMD).
-template <unsigned F, bool LEAF_LDS, bool PK>
-__global__ void __launch_bounds__(1024) render_features_lds(FeatureArgs A, int n_nodes, int stack_entries, int n_leaves) {
-  static_assert((F & F_WIDE) != 0 && (F & F_FRAMES) == 0, "the spheres-only 4-wide walk");
+// The staged 4-wide kernels' prologue: the wide nodes, and with LEAF_LDS the leaf table, copied into the dynamic LDS
+// by the whole workgroup, a barrier, and the scene that reads them there; returns this lane's stack behind them.
+template <bool LEAF_LDS>
+__device__ __forceinline__ int* stage_wide_lds(const Scene& in, int n_nodes, int n_leaves, Scene& S) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int rec = (int)sizeof(rt_wnode), lrec = (int)sizeof(rt_node);
   {
-    const uint4* src = reinterpret_cast<const uint4*>(A.S.wnodes);
+    const uint4* src = reinterpret_cast<const uint4*>(in.wnodes);
     uint4* dst = reinterpret_cast<uint4*>(lds);
     const int n16 = n_nodes * (rec / 16);
     for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
     if constexpr (LEAF_LDS) {
-      const uint4* lsrc = reinterpret_cast<const uint4*>(A.S.leaves);
+      const uint4* lsrc = reinterpret_cast<const uint4*>(in.leaves);
       uint4* ldst = reinterpret_cast<uint4*>(lds + (size_t)n_nodes * rec);
       const int l16 = n_leaves * (lrec / 16);
       for (int i = threadIdx.x; i < l16; i += blockDim.x) ldst[i] = lsrc[i];
     }
   }
   __syncthreads();
-  Scene S = A.S;
+  S = in;
   S.wnodes = reinterpret_cast<const rt_wnode*>(lds);
   if constexpr (LEAF_LDS) S.leaves = reinterpret_cast<const rt_node*>(lds + (size_t)n_nodes * rec);
   else n_leaves = 0;
-  int* stk = reinterpret_cast<int*>(lds + (size_t)n_nodes * rec + (size_t)n_leaves * lrec) + threadIdx.x;
+  return reinterpret_cast<int*>(lds + (size_t)n_nodes * rec + (size_t)n_leaves * lrec) + threadIdx.x;
+}
+
+// LDS-staged 4-wide walk (spheres-only worlds): the wide nodes, the leaf table (LEAF_LDS, its own instantiation
+// as in render_philox2_lds) and the lane stacks, `stack_entries` per lane, copied once per workgroup of up to 16
+// waves; the block size is the launch's (1 to 4 waves per SIMD).
+template <unsigned F, bool LEAF_LDS, bool PK>
+__global__ void __launch_bounds__(1024) render_features_lds(FeatureArgs A, int n_nodes, int stack_entries, int n_leaves) {
+  static_assert((F & F_WIDE) != 0 && (F & F_FRAMES) == 0, "the spheres-only 4-wide walk");
+  Scene S;
+  int* stk = stage_wide_lds<LEAF_LDS>(A.S, n_nodes, n_leaves, S);
   (void)stack_entries;  // (the host sizes the LDS with it: plan_features)
   features_loop<F, PK, false>(A, S, stk, (int)blockDim.x, stk);  // (no frames: the Side slots are never touched)
+}
+
+// ---------------------------------------------------------------- specular-chain feature buffers (rt.h rt_render_features_chain)
+// A first-hit pass's arguments and the chain's. Kernels and a loop of their own, siblings of the first-hit ones,
+// which compile to what they compiled to before.
+struct FeatureChainArgs {
+  FeatureArgs A;
+  int max_bounces;       // 0..RT_CHAIN_MAX_BOUNCES
+  uint32_t chain_flags;  // RT_CHAIN_*
+  double max_fuzz;
+  unsigned long long* counts;  // {ended_miss, ended_cap, bounces}, 0 at launch
+};
+
+// features_loop with the chain of rt.h per sample: first_hit, then the sample ends or the lane scatters and runs
+// first_hit again. The chain loop relies on reconvergence: a lane whose chain has ended leaves the loop and is masked
+// off until the wave's last chain ends, so walk_until's ballots (its `stop` of 0 walks until no active lane walks)
+// and first_hit's live count, which scales leaf_stop, see the lanes still in a chain and nothing else; no lane
+// carries a `walking = false` through a walk it takes no part in. Counts: three integers per lane over all the
+// blocks the wave folds, reduced and added once per wave after the last block (wave_add, as the render loops do).
+// Not once per block: an `if (lane == 0) atomicAdd` at the bottom of the block loop sits next to the claim's
+// `if (lane == 0)` at its top, the compiler threads the one branch into the other, and the wave's lanes no longer
+// meet at the claim's __shfl: the lanes that skipped both read a stale block id and never leave the loop.
+template <unsigned F, bool PK, bool REC>
+__device__ __forceinline__ void features_chain_loop(const FeatureChainArgs& C, const Scene& S, int* stk, int stride,
+                                                    int* side_p) {
+  const FeatureArgs& A = C.A;
+  const int lane = threadIdx.x & 63;
+  const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
+  Side side{side_p, stride};
+  unsigned long long n_miss = 0, n_cap = 0, n_bounce = 0;
+  for (;;) {
+    unsigned long long b = 0;
+    if (lane == 0) b = atomicAdd(A.counter, 1ull);
+    b = __shfl(b, 0);
+    if (b >= A.blocks_total) break;
+    const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
+    const int px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    if (px < A.W && row < A.H) {  // (a lane outside the image idles until the wave's next claim)
+      const uint32_t pid = (uint32_t)((long long)row * A.W + px);
+      double* q = A.sums + (size_t)pid * RT_FEATURE_DOUBLES;
+      double acc[RT_FEATURE_DOUBLES];
+#pragma unroll
+      for (int k = 0; k < RT_FEATURE_DOUBLES; ++k) acc[k] = A.accumulate ? q[k] : 0.0;
+      const int s_end = A.first + A.count;
+      for (int s = A.first; s < s_end; ++s) {
+        RngPhilox g;
+        g.init(A.seed, pid, (uint32_t)s);
+        g.reserve(3);  // the UV pair and the first disk try
+        const double ru = g.draw(), rv = g.draw();
+        const int y = A.H - 1 - row;
+        const double u = ((double)px + ru) / (double)A.W;
+        const double v = ((double)y + rv) / (double)A.H;
+        Ray ray = get_ray(A.cam, u, v, g);
+        V3 thr = v3(1.0, 1.0, 1.0);
+        double len = 0.0;
+        int nb = 0;
+        for (;;) {
+          Hit h;
+          if (!first_hit<F, PK, REC>(S, ray, g, stk, stride, side, joint, A.leaf_stop, h)) {
+            const V3 c = vmul(thr, v3(A.S.bg[0], A.S.bg[1], A.S.bg[2]));
+            acc[RT_FEAT_ALBEDO] = acc[RT_FEAT_ALBEDO] + c.x;
+            acc[RT_FEAT_ALBEDO + 1] = acc[RT_FEAT_ALBEDO + 1] + c.y;
+            acc[RT_FEAT_ALBEDO + 2] = acc[RT_FEAT_ALBEDO + 2] + c.z;
+#pragma unroll
+            for (int k = RT_FEAT_NORMAL; k < RT_FEATURE_DOUBLES; ++k) acc[k] = acc[k] + 0.0;  // (-0.0 + 0.0 is +0.0)
+            ++n_miss;
+            break;
+          }
+          len = len + h.t * sqrt(dot(ray.d, ray.d));
+          const DMat m = S.mats[h.mat];
+          const bool diel = m.type == RT_MAT_DIELECTRIC, metal = m.type == RT_MAT_METAL;
+          const bool follows = diel ? (C.chain_flags & RT_CHAIN_DIELECTRIC) != 0
+                                    : metal && (C.chain_flags & RT_CHAIN_METAL) != 0 && m.param <= C.max_fuzz;
+          // The first-hit rule's albedo, which is also scatter's attenuation of the two followed materials
+          // (Dielectric (1,1,1), Metal its texture): the kernel's one copy of the texture code.
+          const V3 a = diel ? v3(1.0, 1.0, 1.0) : texture_value<F>(S, m.tex, h.u, h.v, h.p);
+          if (!follows || nb >= C.max_bounces) {
+            const V3 c = vmul(thr, a);
+            acc[RT_FEAT_ALBEDO] = acc[RT_FEAT_ALBEDO] + c.x;
+            acc[RT_FEAT_ALBEDO + 1] = acc[RT_FEAT_ALBEDO + 1] + c.y;
+            acc[RT_FEAT_ALBEDO + 2] = acc[RT_FEAT_ALBEDO + 2] + c.z;
+            acc[RT_FEAT_NORMAL] = acc[RT_FEAT_NORMAL] + h.n.x;
+            acc[RT_FEAT_NORMAL + 1] = acc[RT_FEAT_NORMAL + 1] + h.n.y;
+            acc[RT_FEAT_NORMAL + 2] = acc[RT_FEAT_NORMAL + 2] + h.n.z;
+            acc[RT_FEAT_DEPTH] = acc[RT_FEAT_DEPTH] + len;
+            acc[RT_FEAT_HITS] = acc[RT_FEAT_HITS] + 1.0;
+            n_cap += follows;
+            break;
+          }
+          g.rewind();  // (the words buffered before the walk were not carried through it)
+          const V3 d = scatter_specular(m, metal, ray, h, g);
+          ray.o = h.p, ray.d = d;  // (the time stays the sample's)
+          thr = vmul(thr, a);
+          ++nb;
+        }
+        n_bounce += (unsigned)nb;
+      }
+#pragma unroll
+      for (int k = 0; k < RT_FEATURE_DOUBLES; ++k) q[k] = acc[k];
+    }
+  }
+  wave_add(&C.counts[0], n_miss);
+  wave_add(&C.counts[1], n_cap);
+  wave_add(&C.counts[2], n_bounce);
+}
+
+template <unsigned F, bool PK, bool REC>
+__global__ void __launch_bounds__(RT_BLOCK) render_features_chain(FeatureChainArgs C) {
+  __shared__ int stk_mem[(lane_ints<F>() + 1) * RT_BLOCK];
+  features_chain_loop<F, PK, REC>(C, C.A.S, &stk_mem[threadIdx.x], RT_BLOCK,
+                                  &stk_mem[(((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK) + 1) * RT_BLOCK + threadIdx.x]);
+}
+
+// render_features_lds's staging. WAVES: the most waves per SIMD the kernel is launched with (blocks of up to
+// WAVES * 256 threads), which sets its register budget: 3 leaves the chain's state in registers, 4 spills it.
+template <unsigned F, bool LEAF_LDS, bool PK, int WAVES>
+__global__ void __launch_bounds__(WAVES * 256) render_features_chain_lds(FeatureChainArgs C, int n_nodes, int stack_entries,
+                                                                  int n_leaves) {
+  static_assert((F & F_WIDE) != 0 && (F & F_FRAMES) == 0, "the spheres-only 4-wide walk");
+  Scene S;
+  int* stk = stage_wide_lds<LEAF_LDS>(C.A.S, n_nodes, n_leaves, S);
+  (void)stack_entries;
+  features_chain_loop<F, PK, false>(C, S, stk, (int)blockDim.x, stk);
 }
 
 // ---------------------------------------------------------------- debug: per-function probes
@@ -1578,4 +1709,5 @@ const void* philox_kernel_cornell(const KernelForm& f);
 const void* philox_kernel_full(const KernelForm& f);
 const void* philox_kernel_full_dark(const KernelForm& f);
 const void* features_kernel(const FeaturePlan& P);  // rt_k_features.hip (render_features / render_features_lds)
+const void* features_chain_kernel(const FeaturePlan& P);  // rt_k_features_chain.hip (the same forms, with a chain)
 }  // namespace rt

@@ -197,7 +197,7 @@ int plan_launch(const WorldShape& W, const rt_render_params& p, int span_first, 
   return RT_OK;
 }
 
-int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out) {
+int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out, bool chain) {
   FeaturePlan P;
   rt_launch_info& I = P.info;
   const long long blocks = (long long)((p.width + 7) / 8) * ((p.height + 7) / 8);  // (8x8 pixel blocks, one per wave)
@@ -221,14 +221,15 @@ int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKn
     P.pk = wide_keys_packed(W, K);
     P.entries = W.wide_stack_need + 3;  // (wide_node writes 3 slots)
     // LDS-staged like the render's 4-wide kernels: the wide nodes, the leaf table when it fits as well, and the
-    // lane stacks of one workgroup per CU, at the most waves per SIMD (4, or RTAMD_WAVES) that fit kLdsBudget
+    // lane stacks of one workgroup per CU, at the most waves per SIMD (4, a chain pass 3, or RTAMD_WAVES) that fit kLdsBudget
     // with the leaves, else with the nodes alone.
     if (K.lds) {
       auto lds_bytes = [&](int w, bool leaves) {
         return (size_t)W.n_wnodes * sizeof(rt_wnode) + (leaves ? (size_t)W.n_leaves * sizeof(rt_node) : 0) +
                (size_t)P.entries * (w * 256) * sizeof(int);
       };
-      const int w = K.waves ? K.waves : 4;
+      // (a chain pass: 3, the most at which its staged kernels hold the chain's state in registers; rt_kernels.h)
+      const int w = K.waves ? K.waves : chain ? 3 : 4;
       const bool leaves = K.leaf_lds && W.n_leaves > 0 && lds_bytes(w, true) <= kLdsBudget;
       if (lds_bytes(w, leaves) <= kLdsBudget) {
         P.lds = true, P.leaf_lds = leaves;

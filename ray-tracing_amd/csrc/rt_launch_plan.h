@@ -118,6 +118,9 @@ struct FeaturePlan {
 constexpr int kFeatBlocksPerCU = 8;  // global-memory forms: RT_BLOCK-thread blocks queued per CU (4 waves per SIMD)
 // Pure, like plan_launch. Reads of `p` the frame size and RT_FLAG_REFERENCE_CULL; of `K` lds, leaf_lds,
 // packed_keys, waves (the LDS-staged form's), wide, and leaf_stop, trav_stop and box_first (FeaturePlan::leaf_stop).
-int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out);
+// `chain`: a specular-chain pass (rt.h rt_render_features_chain; kernels: rt_k_features_chain.hip): the same forms,
+// the LDS-staged one at 3 waves per SIMD where RTAMD_WAVES does not say otherwise.
+int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out,
+                  bool chain = false);
 
 }  // namespace rt

@@ -65,6 +65,12 @@ struct rt_ctx {
   rt_launch_info last_launch{};  // rt_last_launch
   int last_wide_packed = 0;      // the last 4-wide walk sorted packed keys (rt_debug_wide_keys)
   rt_launch_info last_feature{}; // rt_last_feature_launch
+  // The last chain pass (rt_last_feature_chain): an event of the ctx's own recorded after it (created by the first
+  // chain pass; not ev_done, which later launches record again, and not the caller's stream, which may be gone by
+  // then), pixels * samples, and the device counts {ended_miss, ended_cap, bounces} (fc_counts, below)
+  bool fc_made = false;
+  hipEvent_t ev_fc = nullptr;
+  int64_t fc_samples = 0;
   // rt_render's frame events: after the render launches (gather start), after the gather, after assembly
   hipEvent_t ev_gather = nullptr, ev_gathered = nullptr, ev_asm = nullptr;
   rt_frame_timing last_frame{};  // rt_last_frame_timing
@@ -89,6 +95,7 @@ struct rt_ctx {
   // (colour, V) buffers, its counts; the device copies of a blocking call's inputs and outputs (rt_frame_denoise:
   // the frame's preview and error map), and the scratch counts of that preview's frame_resolve launch
   FrameBuf dn_guide, dn_a, dn_b, dn_counts, dn_color, dn_se, dn_feat, dn_out, dn_rgb, dn_fcounts;
+  FrameBuf fc_counts;
   hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;  // around a blocking denoise call's kernels (kernel_ms)
   rt_denoise_info last_denoise{};                 // rt_last_denoise
   // Progressive frames open on this ctx (rt_frame_*), and what a saved frame records of the scene: the
@@ -223,7 +230,7 @@ void free_frame_bufs(rt_ctx* c) {
   for (rt_ctx::FrameBuf* b : {&c->fb_slab, &c->fb_slab_lin, &c->fb_gather, &c->fb_gather_lin, &c->fb_img,
                               &c->fb_img_lin, &c->fb_gens, &c->fb_partial, &c->fb_tail, &c->fb_acc, &c->dn_guide,
                               &c->dn_a, &c->dn_b, &c->dn_counts, &c->dn_color, &c->dn_se, &c->dn_feat, &c->dn_out,
-                              &c->dn_rgb, &c->dn_fcounts}) {
+                              &c->dn_rgb, &c->dn_fcounts, &c->fc_counts}) {
     (void)hipFree(b->p);
     b->p = nullptr;
     b->bytes = 0;
@@ -676,6 +683,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_done) (void)hipEventDestroy(c->ev_done);
+  if (c->ev_fc) (void)hipEventDestroy(c->ev_fc);
   if (c->ev_gather) (void)hipEventDestroy(c->ev_gather);
   if (c->ev_gathered) (void)hipEventDestroy(c->ev_gathered);
   if (c->ev_asm) (void)hipEventDestroy(c->ev_asm);
@@ -831,22 +839,46 @@ int rt_internal_launch_plan(const rt_scene_desc* desc, uint32_t upload_flags, in
   return RT_OK;
 }
 
-// Internal (rt_internal.h; no device needed): the plan launch_features would make, like rt_internal_launch_plan.
-int rt_internal_features_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p,
-                              rt_launch_info* out, int32_t* out_extra) {
+namespace {
+// rt_render_features_chain's own argument checks (rt.h), before any HIP call and before features_check's.
+int chain_check(const rt_feature_chain* ch) {
+  if (!ch) return invalid("rt_render_features_chain: null argument");
+  if (ch->max_bounces < 0 || ch->max_bounces > RT_CHAIN_MAX_BOUNCES)
+    return invalid("rt_render_features_chain: max_bounces must be in 0..64");
+  if (ch->flags & ~(RT_CHAIN_DIELECTRIC | RT_CHAIN_METAL)) return invalid("rt_render_features_chain: unknown flag bits");
+  if (!(ch->max_fuzz >= 0.0) || ch->max_fuzz == INFINITY)
+    return invalid("rt_render_features_chain: max_fuzz must be finite and >= 0");
+  return RT_OK;
+}
+
+int features_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p, bool chain,
+                  rt_launch_info* out, int32_t* out_extra) {
   if (!desc || !p || !out || cu_count < 1) return invalid("null argument");
   if (p->width <= 0 || p->height <= 0) return invalid("width and height must be positive");
   rt::PreparedScene S;
   int rc = rt::prepare_scene(desc, upload_flags, S);
   if (rc) return rc;
   rt::FeaturePlan P;
-  if ((rc = rt::plan_features(rt::world_shape(S, cu_count), *p, rt::read_knobs(), P))) return rc;
+  if ((rc = rt::plan_features(rt::world_shape(S, cu_count), *p, rt::read_knobs(), P, chain))) return rc;
   *out = P.info;
   if (out_extra) {
     const int32_t extra[RT_FEATURES_PLAN_EXTRA] = {P.n_items, P.entries, P.n_leaves, P.pk, P.leaf_stop};
     std::copy(extra, extra + RT_FEATURES_PLAN_EXTRA, out_extra);
   }
   return RT_OK;
+}
+}  // namespace
+
+// Internal (rt_internal.h; no device needed): the plan launch_features would make, like rt_internal_launch_plan.
+int rt_internal_features_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p,
+                              rt_launch_info* out, int32_t* out_extra) {
+  return features_plan(desc, upload_flags, cu_count, p, false, out, out_extra);
+}
+int rt_internal_features_chain_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count,
+                                    const rt_render_params* p, const rt_feature_chain* chain, rt_launch_info* out,
+                                    int32_t* out_extra) {
+  const int rc = chain_check(chain);
+  return rc ? rc : features_plan(desc, upload_flags, cu_count, p, true, out, out_extra);
 }
 
 int rt_render_shard_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, uint8_t* d_rgb, double* d_lin,
@@ -1057,16 +1089,20 @@ int features_check(const rt_ctx* c, const rt_camera* cam, const rt_render_params
 
 // One feature pass over the whole image on `st`: plan (rt_launch_plan.h plan_features), the block counter back
 // to 0, the kernel. The counter is the ctx's work counter, so the pass takes its place in the ctx's launch
-// order: after the previous tier-B launch (ev_done), and the next one waits for it.
+// order: after the previous tier-B launch (ev_done), and the next one waits for it. `ch`: a chain pass (the same
+// plan, rt_k_features_chain.hip's kernels, its counts zeroed in the ctx's buffer); null: a first-hit pass.
 int launch_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int first, int n, int accumulate,
-                    double* d_sums, hipStream_t st) {
+                    double* d_sums, hipStream_t st, const rt_feature_chain* ch = nullptr) {
   rt::FeaturePlan P;
-  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P);
+  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P, ch != nullptr);
   if (rc) return rc;
-  const void* fn = rt::features_kernel(P);
+  const void* fn = ch ? rt::features_chain_kernel(P) : rt::features_kernel(P);
+  if (ch && (rc = grow(c, c->fc_counts, 3 * sizeof(unsigned long long)))) return rc;
+  if (ch && !c->ev_fc) HIPCHK(hipEventCreateWithFlags(&c->ev_fc, hipEventDisableTiming));
   if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
   c->last_stream = st;
-  FeatureArgs A{};
+  FeatureChainArgs CA{};
+  FeatureArgs& A = CA.A;
   A.S = c->scene;
   A.cam = *cam;
   A.W = p->width, A.H = p->height;
@@ -1079,14 +1115,40 @@ int launch_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, 
   A.counter = c->d_counter;
   A.sums = d_sums;
   HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), st));
+  if (ch) {
+    CA.max_bounces = ch->max_bounces, CA.chain_flags = ch->flags, CA.max_fuzz = ch->max_fuzz;
+    CA.counts = (unsigned long long*)c->fc_counts.p;
+    HIPCHK(hipMemsetAsync(c->fc_counts.p, 0, 3 * sizeof(unsigned long long), st));
+  }
   const int lds = P.info.dyn_lds_bytes;
   if (lds) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   int n_items = P.n_items, entries = P.entries, n_leaves = P.n_leaves;
-  void* args[] = {&A, &n_items, &entries, &n_leaves};  // (the global-memory kernels take the first alone)
+  // (the global-memory kernels take the first alone; a first-hit kernel the FeatureArgs at the head of `CA`)
+  void* args[] = {ch ? (void*)&CA : (void*)&A, &n_items, &entries, &n_leaves};
   HIPCHK(hipLaunchKernel(fn, dim3(P.info.grid), dim3(P.info.block), args, (size_t)lds, st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_done, st));
   c->last_feature = P.info;
+  if (ch) {
+    HIPCHK(hipEventRecord(c->ev_fc, st));
+    c->fc_made = true;
+    c->fc_samples = (int64_t)p->width * p->height * n;
+  }
+  return RT_OK;
+}
+
+// The blocking calls' body: a device copy of the caller's sums around the pass on the ctx's stream.
+int features_blocking(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* ch, int first,
+                      int n, int accumulate, double* sums) {
+  DEVICE_SCOPE(c->device);
+  const size_t bytes = sizeof(double) * RT_FEATURE_DOUBLES * (size_t)p->width * (size_t)p->height;
+  DevBuf buf;
+  HIPCHK(hipMalloc(&buf.p, bytes));
+  if (accumulate) HIPCHK(hipMemcpy(buf.p, sums, bytes, hipMemcpyHostToDevice));
+  const int rc = launch_features(c, cam, p, first, n, accumulate, (double*)buf.p, c->stream, ch);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(sums, buf.p, bytes, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 }  // namespace
@@ -1103,15 +1165,37 @@ int rt_render_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
                        int accumulate, double* sums) {
   int rc = features_check(c, cam, p, first_sample, n_samples, sums);
   if (rc) return rc;
+  return features_blocking(c, cam, p, nullptr, first_sample, n_samples, accumulate, sums);
+}
+
+int rt_render_features_chain_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                                   int first_sample, int n_samples, int accumulate, double* d_sums, void* stream) {
+  int rc = chain_check(chain);
+  if (rc || (rc = features_check(c, cam, p, first_sample, n_samples, d_sums))) return rc;
   DEVICE_SCOPE(c->device);
-  const size_t bytes = sizeof(double) * RT_FEATURE_DOUBLES * (size_t)p->width * (size_t)p->height;
-  DevBuf buf;
-  HIPCHK(hipMalloc(&buf.p, bytes));
-  if (accumulate) HIPCHK(hipMemcpy(buf.p, sums, bytes, hipMemcpyHostToDevice));
-  rc = launch_features(c, cam, p, first_sample, n_samples, accumulate, (double*)buf.p, c->stream);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(sums, buf.p, bytes, hipMemcpyDeviceToHost));
+  return launch_features(c, cam, p, first_sample, n_samples, accumulate, d_sums, (hipStream_t)stream, chain);
+}
+
+int rt_render_features_chain(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                             int first_sample, int n_samples, int accumulate, double* sums) {
+  int rc = chain_check(chain);
+  if (rc || (rc = features_check(c, cam, p, first_sample, n_samples, sums))) return rc;
+  return features_blocking(c, cam, p, chain, first_sample, n_samples, accumulate, sums);
+}
+
+int rt_last_feature_chain(rt_ctx* c, rt_feature_chain_stats* out) {
+  if (!c || !out) return invalid("null argument");
+  if (!c->fc_made) {
+    rt::set_error("rt_last_feature_chain: no chain pass was made");
+    return RT_E_STATE;
+  }
+  DEVICE_SCOPE(c->device);
+  unsigned long long k[3];  // {ended_miss, ended_cap, bounces}
+  HIPCHK(hipEventSynchronize(c->ev_fc));
+  HIPCHK(hipMemcpy(k, c->fc_counts.p, sizeof k, hipMemcpyDeviceToHost));
+  out->samples = c->fc_samples;
+  out->ended_miss = (int64_t)k[0], out->ended_cap = (int64_t)k[1], out->bounces = (int64_t)k[2];
+  out->ended_surface = out->samples - out->ended_miss - out->ended_cap;
   return RT_OK;
 }
 

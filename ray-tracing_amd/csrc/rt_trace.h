@@ -1865,4 +1865,33 @@ __device__ __forceinline__ void scatter(const Scene& S, const DMat& m, const Ray
   }
 }
 
+// The specular cut of scatter(): the scattered direction of a Metal (`metal`) or a Dielectric hit, from the same
+// draws in the same order and the same operations as above, so the same bits (the specular-chain feature pass,
+// rt.h rt_render_features_chain; scatter's own s.ray.o = h.p, s.ray.tm = r.tm and attenuation are the caller's).
+// No Lambertian, light or isotropic code. Metal's sqrt(b) above is Lambertian's alone; its fuzz term is added at
+// fuzz 0 too (the sign of a zero component can differ).
+template <class R>
+__device__ __forceinline__ V3 scatter_specular(const DMat& m, bool metal, const Ray& r, const Hit& h, R& g) {
+  g.reserve(2);  // Metal draws 2, Dielectric 1
+  V3 v = v3(1, 0, 0);
+  if (metal) {
+    const double a = g.draw(), b = g.draw();
+    const double ang = 2.0 * kPi * a;
+    double sn, cs;
+    if constexpr (kFusedSincos<R::kSL>) m_sincos<R::kSL>(ang, sn, cs);
+    else cs = m_cos<R::kSL>(ang), sn = m_sin<R::kSL>(ang);
+    const double z = (b * 2.0) - 1.0;
+    const double q = sqrt(1.0 - z * z);
+    v = v3(q * cs, q * sn, z);
+  }
+  const V3 ud = unit(r.d);
+  if (metal) return reflect(ud, h.n) + scale(m.param, v);
+  const double eta = h.ff ? 1.0 / m.param : m.param;
+  const double cos_theta = gmin(dot(vneg(ud), h.n), 1.0);
+  const double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
+  const double rd = g.draw();
+  if ((eta * sin_theta > 1.0) || rd < schlick(cos_theta, eta)) return reflect(ud, h.n);
+  return refract(ud, h.n, eta);
+}
+
 }  // namespace rtd

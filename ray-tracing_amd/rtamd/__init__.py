@@ -185,6 +185,16 @@ class rt_denoise_info(C.Structure):
     _fields_ = [("device_allocs", C.c_int32), ("launches", C.c_int32), ("lds_bytes", C.c_int32), ("_pad", C.c_int32)]
 
 
+class rt_feature_chain(C.Structure):
+    _fields_ = [("max_bounces", C.c_int32), ("flags", C.c_uint32), ("max_fuzz", C.c_double)]
+
+
+class rt_feature_chain_stats(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("ended_surface", C.c_int64), ("ended_miss", C.c_int64),
+                ("ended_cap", C.c_int64), ("bounces", C.c_int64)]
+
+
+assert C.sizeof(rt_feature_chain) == 16 and C.sizeof(rt_feature_chain_stats) == 40
 assert C.sizeof(rt_denoise_params) == 56 and C.sizeof(rt_denoise_stats) == 40 and C.sizeof(rt_denoise_info) == 16
 assert C.sizeof(rt_frame_ckpt_desc) == 344
 assert C.sizeof(rt_error_tol) == 16 and C.sizeof(rt_error_stats) == 48
@@ -217,6 +227,7 @@ EXPORTED = [
     "rt_frame_resume", "rt_frame_resume_shard", "rt_frame_shard_stops", "rt_frame_checkpoint_header",
     "rt_render_features", "rt_render_features_async", "rt_last_feature_launch", "rt_features_resolve",
     "rt_denoise_host", "rt_denoise", "rt_denoise_async", "rt_last_denoise", "rt_frame_denoise",
+    "rt_render_features_chain", "rt_render_features_chain_async", "rt_last_feature_chain",
 ]
 
 # The feature-guided denoiser's flags (rt.h)
@@ -227,6 +238,8 @@ RT_DENOISE_MAX_ITERATIONS = 8
 
 # First-hit feature buffers (rt.h): doubles per pixel of a feature pass's sums, and where each feature starts
 RT_FEATURE_DOUBLES, RT_FEAT_ALBEDO, RT_FEAT_NORMAL, RT_FEAT_DEPTH, RT_FEAT_HITS = 8, 0, 3, 6, 7
+# Specular-chain feature buffers (rt.h): which materials a chain follows, and the most scatters it may follow
+RT_CHAIN_DIELECTRIC, RT_CHAIN_METAL, RT_CHAIN_MAX_BOUNCES = 1, 2, 64
 
 # include/rt_wide.h: one 4-wide node (128 B)
 WNODE_DTYPE = np.dtype([("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("child", "<i4", (4,)), ("pad", "<i4", (4,))])
@@ -354,6 +367,11 @@ def lib() -> C.CDLL:
                                              C.c_void_p]),
             "rt_last_feature_launch": (I, [C.c_void_p, P(rt_launch_info)]),
             "rt_features_resolve": (I, [P(D), C.c_int64, I, P(D), P(D), P(D), P(D), P(C.c_uint8)]),
+            "rt_render_features_chain": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(rt_feature_chain), I, I,
+                                             I, P(D)]),
+            "rt_render_features_chain_async": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(rt_feature_chain),
+                                                   I, I, I, C.c_void_p, C.c_void_p]),
+            "rt_last_feature_chain": (I, [C.c_void_p, P(rt_feature_chain_stats)]),
             "rt_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8), P(rt_denoise_stats)]),
             "rt_internal_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8),
                                              P(rt_denoise_stats), P(D)]),
@@ -821,11 +839,13 @@ class Context:
         return {k: getattr(info, k) for k, _ in rt_launch_info._fields_}
 
     def render_features(self, cam: rt_camera, params: rt_render_params, first_sample: int = 0,
-                        n_samples: Optional[int] = None, into: Optional[np.ndarray] = None) -> np.ndarray:
+                        n_samples: Optional[int] = None, into: Optional[np.ndarray] = None,
+                        chain: Optional["rt_feature_chain"] = None) -> np.ndarray:
         """rt_render_features: the first-hit feature sums of samples first_sample .. first_sample + n_samples - 1
         (default: params.spp samples), (H, W, 8) doubles: albedo 0:3, normal 3:6, depth 6, hits 7, each the
         sample-order sum (`resolve_features` makes the images). `into` (H, W, 8, float64, C order) is accumulated
-        onto in place and returned. Blocking."""
+        onto in place and returned. Blocking. `chain` (`make_feature_chain`): rt_render_features_chain, the features
+        at the end of each sample's specular chain instead (`last_feature_chain` has its counts)."""
         W, H = params.width, params.height
         n = params.spp if n_samples is None else n_samples
         if into is None:
@@ -834,18 +854,34 @@ class Context:
             sums = into
             if sums.dtype != np.float64 or sums.shape != (H, W, RT_FEATURE_DOUBLES) or not sums.flags.c_contiguous:
                 raise RTError("render_features: `into` must be a C-contiguous float64 array of shape (H, W, 8)")
-        _check(lib().rt_render_features(self._h, C.byref(cam), C.byref(params), int(first_sample), int(n),
-                                        int(into is not None), sums.ctypes.data_as(C.POINTER(C.c_double))),
-               "rt_render_features")
+        tail = (int(first_sample), int(n), int(into is not None), sums.ctypes.data_as(C.POINTER(C.c_double)))
+        if chain is None:
+            _check(lib().rt_render_features(self._h, C.byref(cam), C.byref(params), *tail), "rt_render_features")
+        else:
+            _check(lib().rt_render_features_chain(self._h, C.byref(cam), C.byref(params), C.byref(chain), *tail),
+                   "rt_render_features_chain")
         return sums
 
     def render_features_async(self, cam, params, d_sums: int, first_sample: int = 0, n_samples: Optional[int] = None,
-                              accumulate: bool = False, stream: int = 0):
-        """rt_render_features_async: the same pass queued on `stream` into device memory (H*W*8 doubles)."""
+                              accumulate: bool = False, stream: int = 0,
+                              chain: Optional["rt_feature_chain"] = None):
+        """rt_render_features_async: the same pass queued on `stream` into device memory (H*W*8 doubles); with a
+        `chain`, rt_render_features_chain_async."""
         n = params.spp if n_samples is None else n_samples
-        _check(lib().rt_render_features_async(self._h, C.byref(cam), C.byref(params), int(first_sample), int(n),
-                                              int(accumulate), C.c_void_p(d_sums), C.c_void_p(stream or None)),
-               "rt_render_features_async")
+        tail = (int(first_sample), int(n), int(accumulate), C.c_void_p(d_sums), C.c_void_p(stream or None))
+        if chain is None:
+            _check(lib().rt_render_features_async(self._h, C.byref(cam), C.byref(params), *tail),
+                   "rt_render_features_async")
+        else:
+            _check(lib().rt_render_features_chain_async(self._h, C.byref(cam), C.byref(params), C.byref(chain), *tail),
+                   "rt_render_features_chain_async")
+
+    def last_feature_chain(self) -> dict:
+        """rt_last_feature_chain: the exact counts of the last chain pass (samples, ended_surface, ended_miss,
+        ended_cap, bounces). Waits for that pass when it was queued with `render_features_async`."""
+        st = rt_feature_chain_stats()
+        _check(lib().rt_last_feature_chain(self._h, C.byref(st)), "rt_last_feature_chain")
+        return {k: getattr(st, k) for k, _ in rt_feature_chain_stats._fields_}
 
     def last_feature_launch(self) -> dict:
         """rt_last_feature_launch: which kernel form the last feature pass ran (loop 2: the 4-wide walk, 1: the
@@ -925,6 +961,18 @@ class Context:
                                    y.ctypes.data_as(P(C.c_double)), x.size, out.ctypes.data_as(P(C.c_double))),
                "rt_debug_math")
         return out
+
+
+def make_feature_chain(max_bounces: int = 8, dielectric: bool = True, metal: bool = True,
+                       max_fuzz: float = 0.0) -> rt_feature_chain:
+    """The chain of a specular-chain feature pass (rt.h rt_feature_chain): follow up to `max_bounces` specular
+    scatters through Dielectrics and through Metals of fuzz <= max_fuzz. `Context.last_feature_chain()` tells
+    how many samples ended at the cap."""
+    ch = rt_feature_chain()
+    ch.max_bounces = int(max_bounces)
+    ch.flags = (RT_CHAIN_DIELECTRIC if dielectric else 0) | (RT_CHAIN_METAL if metal else 0)
+    ch.max_fuzz = float(max_fuzz)
+    return ch
 
 
 def resolve_features(sums: np.ndarray, n_samples: int) -> dict:
