@@ -627,6 +627,81 @@ int rt_render_features_chain_async(rt_ctx* ctx, const rt_camera* cam, const rt_r
 int rt_last_feature_chain(rt_ctx* ctx, rt_feature_chain_stats* out);
 
 /*
+ * Material-ID coverage buffers: per pixel, which share of its samples saw which material (an anti-aliased ID matte
+ * in the Cryptomatte style). Tier B only. Material ids only: rt_scene_desc's material indices. (Object ids would
+ * need a primitive id in the hit record, which the render kernels do not carry.) Every output is an integer or
+ * one IEEE division of two integers, so host and device agree bit for bit.
+ *
+ * Sample id. For pixel pid = row*W + px and sample s the ray, the stream and the closest hit are the first-hit
+ * feature pass's (rt_render_features: the same UV pair, getRay, tie rule and keyed medium draw;
+ * RT_FLAG_REFERENCE_CULL is honoured). With chain == NULL the sample's id is the hit's material index, or
+ * RT_ID_MISS on a miss. With a chain, the chain is followed exactly as rt_render_features_chain defines it (steps
+ * 1-6 above) and the id is the material of the vertex where it ends (step 5), or RT_ID_MISS when it ends in a miss
+ * (step 2); max_bounces = 0 or flags = 0 give the chain == NULL records bit for bit. A ConstantMedium's id is its
+ * phase material.
+ *
+ * Record and fold. One rt_id_record per pixel, image order. Samples first_sample .. first_sample + n_samples - 1
+ * are folded in sample order from a zero record, or from the caller's record with `accumulate`. Per sample id x:
+ * the first slot with count > 0 and id == x has its count incremented; if there is none, the first slot with
+ * count == 0 takes id = x, count = 1; if there is none, `other` is incremented; `samples` is incremented always.
+ * So slots appear in order of first appearance, the record is the whole state (folding [a,b) and then [b,c) with
+ * `accumulate` gives the record of [a,c) byte for byte), and while other == 0 the slots are the exact histogram of
+ * the pixel's ids. Saturation: a record whose `samples` is UINT32_MAX is full, and a sample folded into it leaves it
+ * unchanged (a guard on the device and in rt_ids_fold_host alike; one call folds at most INT32_MAX samples, so it
+ * can only be reached by accumulating).
+ *
+ * rt_render_ids        blocking, records in host memory (read first with `accumulate`).
+ * rt_render_ids_async  the same pass queued on `stream` into device memory. Both follow the feature passes'
+ *     contract: ordered through the ctx's tier-B launches, no effect on the renders around them, the first device
+ *     of a multi-device ctx, the same kernel forms, reported by rt_last_feature_launch. RT_E_INVALID, before any
+ *     HIP call: everything rt_render_features rejects (shard_count > 1 included) and, with a non-null chain, what
+ *     rt_render_features_chain rejects of it. RT_E_STATE without a scene. With a non-null chain
+ *     rt_last_feature_chain reports the pass's counts as for a chain feature pass (a pass without a chain leaves
+ *     the last chain pass's counts in place).
+ * rt_ids_fold_host     host only: folds ids[0..n) in order into *rec by the rule above (n >= 0).
+ * rt_ids_resolve       host only: per pixel the seven slots sorted by count descending, then id ascending:
+ *     out_rank_ids[7*i + k], out_rank_cov[7*i + k] = count / samples (one division); a free slot gives RT_ID_MISS
+ *     and 0.0; out_other_cov[i] = other / samples. A record with samples == 0 gives 0.0 for every coverage (no
+ *     division is made). Any output may be NULL.
+ * rt_ids_matte_host, rt_ids_matte (blocking, host arrays through the device), rt_ids_matte_async (device arrays, on
+ *     `stream`, ordered like a feature pass)   the matte of a set of ids: `ids` is a host array in every variant,
+ *     strictly ascending, 1 <= n_ids <= RT_ID_MATTE_MAX (else RT_E_INVALID; RT_ID_MISS is a legal member: the sky
+ *     matte). cov = (sum of the counts of the used slots whose id is in the list) / samples, the integer sum first,
+ *     then one division (0.0 when samples == 0); out_cov[i] = cov, out_u8[i] = (uint8_t)(cov * 255.0 + 0.5). Either
+ *     output may be NULL, not both. Host and device run one per-pixel text and give equal bytes.
+ * rt_ids_preview_host, rt_ids_preview (blocking), rt_ids_preview_async   a false-colour image of the records, 3 bytes
+ *     per pixel. The colour of an id x is, per channel c = 0,1,2, ((rt_ids_fmix32(x) >> 8*c) & 255) / 255.0, and
+ *     black for RT_ID_MISS; rt_ids_fmix32 is MurmurHash3's 32-bit finaliser (public domain): h ^= h >> 16,
+ *     h *= 0x85ebca6b, h ^= h >> 13, h *= 0xc2b2ae35, h ^= h >> 16. Channel value = the sum over the slots k in slot
+ *     order of (count_k / samples) * colour_k(c), from 0.0, no contraction; the byte as in the matte.
+ */
+#define RT_ID_SLOTS 7
+#define RT_ID_MISS 0xFFFFFFFFu
+#define RT_ID_MATTE_MAX 1024
+typedef struct rt_id_record {
+    uint32_t id[RT_ID_SLOTS];     /* 0 in a free slot */
+    uint32_t count[RT_ID_SLOTS];  /* 0 = free */
+    uint32_t other;               /* samples whose id found no slot */
+    uint32_t samples;             /* samples folded in all */
+} rt_id_record;                   /* 64 bytes: a feature vector's size, one contiguous store per lane */
+int rt_render_ids(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                  int first_sample, int n_samples, int accumulate, rt_id_record* records);
+int rt_render_ids_async(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                        int first_sample, int n_samples, int accumulate, rt_id_record* d_records, void* stream);
+int rt_ids_fold_host(rt_id_record* rec, const uint32_t* ids, int64_t n);
+int rt_ids_resolve(const rt_id_record* recs, int64_t pixels, uint32_t* out_rank_ids, double* out_rank_cov,
+                   double* out_other_cov);
+int rt_ids_matte_host(const rt_id_record* recs, int64_t pixels, const uint32_t* ids, int n_ids, double* out_cov,
+                      uint8_t* out_u8);
+int rt_ids_matte(rt_ctx* ctx, const rt_id_record* recs, int64_t pixels, const uint32_t* ids, int n_ids,
+                 double* out_cov, uint8_t* out_u8);
+int rt_ids_matte_async(rt_ctx* ctx, const rt_id_record* d_recs, int64_t pixels, const uint32_t* ids, int n_ids,
+                       double* d_out_cov, uint8_t* d_out_u8, void* stream);
+int rt_ids_preview_host(const rt_id_record* recs, int64_t pixels, uint8_t* out_rgb8);
+int rt_ids_preview(rt_ctx* ctx, const rt_id_record* recs, int64_t pixels, uint8_t* out_rgb8);
+int rt_ids_preview_async(rt_ctx* ctx, const rt_id_record* d_recs, int64_t pixels, uint8_t* d_out_rgb8, void* stream);
+
+/*
  * Feature-guided denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with SVGF-style variance
  * guidance over a linear image, its per-pixel standard error (optional) and the feature sums of a feature pass
  * (above). Tier-independent; every array is in image order (row 0 = top). fp64 throughout, no contraction, only

@@ -91,6 +91,15 @@ extern "C" int rt_internal_features_chain_plan(const rt_scene_desc* desc, uint32
                                                const rt_render_params* p, const rt_feature_chain* chain,
                                                rt_launch_info* out, int32_t* out_extra);
 
+// The same for a material-ID pass (rt_render_ids; `chain` may be null): the chain pass's plan, launched with
+// rt_k_ids.hip's kernels. And the hipMalloc calls the ctx's last rt_render_ids*, rt_ids_matte* or rt_ids_preview*
+// call made (-1: null ctx), for the tests: a repeat of one size makes none.
+struct rt_ctx;
+extern "C" int rt_internal_ids_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count,
+                                    const rt_render_params* p, const rt_feature_chain* chain, rt_launch_info* out,
+                                    int32_t* out_extra);
+extern "C" int rt_internal_ids_allocs(rt_ctx* ctx);
+
 // rt_denoise_host (rt.h) with one more output for the tests: out_variance (may be null) = V of every pixel after
 // the last iteration, W*H doubles in image order, which the ABI keeps to itself.
 extern "C" int rt_internal_denoise_host(const rt_denoise_params* params, const double* color, const double* se,

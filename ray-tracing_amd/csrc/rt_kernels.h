@@ -17,6 +17,7 @@
 #include "rt.h"
 #include "rt_device.h"
 #include "rt_error.h"
+#include "rt_ids.h"
 #include "rt_internal.h"
 #include "rt_launch_plan.h"
 #include "rt_trace.h"
@@ -1521,6 +1522,108 @@ __global__ void __launch_bounds__(WAVES * 256) render_features_chain_lds(Feature
   features_chain_loop<F, PK, false>(C, S, stk, (int)blockDim.x, stk);
 }
 
+// ---------------------------------------------------------------- material-ID coverage buffers (rt.h rt_render_ids)
+// A chain pass's arguments: A.sums is the pass's rt_id_record array (64 bytes per pixel, as a feature vector), a
+// pass without a chain has max_bounces = 0, and `counts` may be null (then nothing is counted).
+using IdArgs = FeatureChainArgs;
+
+// features_chain_loop's nest (its comment says why it has this shape: ended lanes leave the chain loop and
+// reconverge, first_hit's ballot sees the lanes still in a chain, the counts go through wave_add after the block
+// loop) with a sample's id where that loop takes its features: the material of the chain's terminal vertex, or
+// RT_ID_MISS, folded into the lane's record by rt_ids.h's ids_fold_one, whose slots are compared and updated under
+// predicates and so stay in registers. No throughput, no path length, no albedo: the kernel has no texture code.
+// One loop for both modes: a pass without a chain runs it with max_bounces = 0, where no material is followed.
+template <unsigned F, bool PK, bool REC>
+__device__ __forceinline__ void ids_loop(const IdArgs& C, const Scene& S, int* stk, int stride, int* side_p) {
+  const FeatureArgs& A = C.A;
+  const int lane = threadIdx.x & 63;
+  const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
+  Side side{side_p, stride};
+  unsigned long long n_miss = 0, n_cap = 0, n_bounce = 0;
+  for (;;) {
+    unsigned long long b = 0;
+    if (lane == 0) b = atomicAdd(A.counter, 1ull);
+    b = __shfl(b, 0);
+    if (b >= A.blocks_total) break;
+    const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
+    const int px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    if (px < A.W && row < A.H) {  // (a lane outside the image idles until the wave's next claim)
+      const uint32_t pid = (uint32_t)((long long)row * A.W + px);
+      uint4* q = reinterpret_cast<uint4*>(A.sums) + (size_t)pid * 4;  // (hipMalloc'd: 16-byte aligned records)
+      static_assert(sizeof(rt_id_record) == 64 && sizeof(rt_id_record) == sizeof(double) * RT_FEATURE_DOUBLES, "rt.h");
+      // the record, field by field in rt.h's order: id[7], count[7], other, samples
+      const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+      const uint4 w0 = A.accumulate ? q[0] : z, w1 = A.accumulate ? q[1] : z, w2 = A.accumulate ? q[2] : z,
+                  w3 = A.accumulate ? q[3] : z;
+      rt_id_record r;
+      r.id[0] = w0.x, r.id[1] = w0.y, r.id[2] = w0.z, r.id[3] = w0.w, r.id[4] = w1.x, r.id[5] = w1.y, r.id[6] = w1.z;
+      r.count[0] = w1.w, r.count[1] = w2.x, r.count[2] = w2.y, r.count[3] = w2.z, r.count[4] = w2.w;
+      r.count[5] = w3.x, r.count[6] = w3.y, r.other = w3.z, r.samples = w3.w;
+      const int s_end = A.first + A.count;
+      for (int s = A.first; s < s_end; ++s) {
+        RngPhilox g;
+        g.init(A.seed, pid, (uint32_t)s);
+        g.reserve(3);  // the UV pair and the first disk try
+        const double ru = g.draw(), rv = g.draw();
+        const int y = A.H - 1 - row;
+        const double u = ((double)px + ru) / (double)A.W;
+        const double v = ((double)y + rv) / (double)A.H;
+        Ray ray = get_ray(A.cam, u, v, g);
+        int nb = 0;
+        uint32_t id = RT_ID_MISS;
+        for (;;) {
+          Hit h;
+          if (!first_hit<F, PK, REC>(S, ray, g, stk, stride, side, joint, A.leaf_stop, h)) {
+            ++n_miss;
+            break;
+          }
+          const DMat m = S.mats[h.mat];
+          const bool diel = m.type == RT_MAT_DIELECTRIC, metal = m.type == RT_MAT_METAL;
+          const bool follows = diel ? (C.chain_flags & RT_CHAIN_DIELECTRIC) != 0
+                                    : metal && (C.chain_flags & RT_CHAIN_METAL) != 0 && m.param <= C.max_fuzz;
+          if (!follows || nb >= C.max_bounces) {
+            id = (uint32_t)h.mat;
+            n_cap += follows;
+            break;
+          }
+          g.rewind();  // (the words buffered before the walk were not carried through it)
+          const V3 d = scatter_specular(m, metal, ray, h, g);
+          ray.o = h.p, ray.d = d;  // (the time stays the sample's)
+          ++nb;
+        }
+        n_bounce += (unsigned)nb;
+        rt::ids_fold_one(r, id);
+      }
+      q[0] = make_uint4(r.id[0], r.id[1], r.id[2], r.id[3]);
+      q[1] = make_uint4(r.id[4], r.id[5], r.id[6], r.count[0]);
+      q[2] = make_uint4(r.count[1], r.count[2], r.count[3], r.count[4]);
+      q[3] = make_uint4(r.count[5], r.count[6], r.other, r.samples);
+    }
+  }
+  if (C.counts) {  // (uniform: a kernel argument)
+    wave_add(&C.counts[0], n_miss);
+    wave_add(&C.counts[1], n_cap);
+    wave_add(&C.counts[2], n_bounce);
+  }
+}
+
+template <unsigned F, bool PK, bool REC>
+__global__ void __launch_bounds__(RT_BLOCK) render_ids(IdArgs C) {
+  __shared__ int stk_mem[(lane_ints<F>() + 1) * RT_BLOCK];
+  ids_loop<F, PK, REC>(C, C.A.S, &stk_mem[threadIdx.x], RT_BLOCK,
+                       &stk_mem[(((F & (F_WIDE | F_MIXW)) ? RT_WSTACK : RT_STACK) + 1) * RT_BLOCK + threadIdx.x]);
+}
+
+// render_features_chain_lds's staging and WAVES.
+template <unsigned F, bool LEAF_LDS, bool PK, int WAVES>
+__global__ void __launch_bounds__(WAVES * 256) render_ids_lds(IdArgs C, int n_nodes, int stack_entries, int n_leaves) {
+  static_assert((F & F_WIDE) != 0 && (F & F_FRAMES) == 0, "the spheres-only 4-wide walk");
+  Scene S;
+  int* stk = stage_wide_lds<LEAF_LDS>(C.A.S, n_nodes, n_leaves, S);
+  (void)stack_entries;
+  ids_loop<F, PK, false>(C, S, stk, (int)blockDim.x, stk);
+}
+
 // ---------------------------------------------------------------- debug: per-function probes
 // The hot-path functions one at a time on device inputs (rt_debug_probe; layouts in rt.h and
 // oracle/oracle.c oracle_probe): record i draws from its own tier-B Philox stream (key = seed, pid = i,
@@ -1710,4 +1813,5 @@ const void* philox_kernel_full(const KernelForm& f);
 const void* philox_kernel_full_dark(const KernelForm& f);
 const void* features_kernel(const FeaturePlan& P);  // rt_k_features.hip (render_features / render_features_lds)
 const void* features_chain_kernel(const FeaturePlan& P);  // rt_k_features_chain.hip (the same forms, with a chain)
+const void* ids_kernel(const FeaturePlan& P);  // rt_k_ids.hip (the same forms: render_ids / render_ids_lds)
 }  // namespace rt

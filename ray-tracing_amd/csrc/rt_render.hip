@@ -96,6 +96,10 @@ struct rt_ctx {
   // the frame's preview and error map), and the scratch counts of that preview's frame_resolve launch
   FrameBuf dn_guide, dn_a, dn_b, dn_counts, dn_color, dn_se, dn_feat, dn_out, dn_rgb, dn_fcounts;
   FrameBuf fc_counts;
+  // Material-ID buffers (rt_render_ids, rt_ids_matte*, rt_ids_preview*): a matte's id list on the device, the device
+  // copies of a blocking call's records and outputs, and the hipMalloc calls the last of those calls made
+  FrameBuf id_list, id_recs, id_cov, id_u8;
+  int id_allocs = 0;
   hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;  // around a blocking denoise call's kernels (kernel_ms)
   rt_denoise_info last_denoise{};                 // rt_last_denoise
   // Progressive frames open on this ctx (rt_frame_*), and what a saved frame records of the scene: the
@@ -230,7 +234,7 @@ void free_frame_bufs(rt_ctx* c) {
   for (rt_ctx::FrameBuf* b : {&c->fb_slab, &c->fb_slab_lin, &c->fb_gather, &c->fb_gather_lin, &c->fb_img,
                               &c->fb_img_lin, &c->fb_gens, &c->fb_partial, &c->fb_tail, &c->fb_acc, &c->dn_guide,
                               &c->dn_a, &c->dn_b, &c->dn_counts, &c->dn_color, &c->dn_se, &c->dn_feat, &c->dn_out,
-                              &c->dn_rgb, &c->dn_fcounts, &c->fc_counts}) {
+                              &c->dn_rgb, &c->dn_fcounts, &c->fc_counts, &c->id_list, &c->id_recs, &c->id_cov, &c->id_u8}) {
     (void)hipFree(b->p);
     b->p = nullptr;
     b->bytes = 0;
@@ -1197,6 +1201,192 @@ int rt_last_feature_chain(rt_ctx* c, rt_feature_chain_stats* out) {
   out->ended_miss = (int64_t)k[0], out->ended_cap = (int64_t)k[1], out->bounces = (int64_t)k[2];
   out->ended_surface = out->samples - out->ended_miss - out->ended_cap;
   return RT_OK;
+}
+
+// ------------------------------------------------------------------ material-ID coverage buffers (rt.h)
+namespace {
+// rt_render_ids' argument checks: the chain's when there is one, then the feature pass's (the ctx last).
+int ids_check(const rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* ch, int first,
+              int n, const rt_id_record* recs) {
+  int rc = ch ? chain_check(ch) : RT_OK;
+  if (!rc) rc = features_check(c, cam, p, first, n, reinterpret_cast<const double*>(recs));
+  if (rc) {  // (the shared checks name the feature passes)
+    std::string msg = rt::last_error();
+    const size_t colon = msg.find(": ");
+    rt::set_error("rt_render_ids" + (colon == std::string::npos ? ": " + msg : msg.substr(colon)));
+  }
+  return rc;
+}
+
+// launch_features for an id pass: the same plan (a staged pass at the chain passes' 3 waves per SIMD: its kernels
+// hold the same walk and chain state), rt_k_ids.hip's kernel, the same place in the ctx's launch order. One kernel
+// for both modes: without a chain it runs with max_bounces = 0 and counts nothing.
+int launch_ids(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* ch, int first, int n,
+               int accumulate, rt_id_record* d_recs, hipStream_t st) {
+  rt::FeaturePlan P;
+  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P, true);
+  if (rc) return rc;
+  const void* fn = rt::ids_kernel(P);
+  if (ch && (rc = grow(c, c->fc_counts, 3 * sizeof(unsigned long long)))) return rc;
+  if (ch && !c->ev_fc) HIPCHK(hipEventCreateWithFlags(&c->ev_fc, hipEventDisableTiming));
+  if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
+  c->last_stream = st;
+  IdArgs CA{};
+  FeatureArgs& A = CA.A;
+  A.S = c->scene;
+  A.cam = *cam;
+  A.W = p->width, A.H = p->height;
+  A.flags = cull(c, p->flags);
+  A.seed = p->seed;
+  A.first = first, A.count = n, A.accumulate = accumulate;
+  A.leaf_stop = P.leaf_stop;
+  A.blocks_x = (p->width + 7) / 8;
+  A.blocks_total = (unsigned long long)P.info.work_items;
+  A.counter = c->d_counter;
+  A.sums = reinterpret_cast<double*>(d_recs);  // (64 bytes per pixel, as a feature vector)
+  HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned long long), st));
+  if (ch) {
+    CA.max_bounces = ch->max_bounces, CA.chain_flags = ch->flags, CA.max_fuzz = ch->max_fuzz;
+    CA.counts = (unsigned long long*)c->fc_counts.p;
+    HIPCHK(hipMemsetAsync(c->fc_counts.p, 0, 3 * sizeof(unsigned long long), st));
+  }
+  const int lds = P.info.dyn_lds_bytes;
+  if (lds) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  int n_items = P.n_items, entries = P.entries, n_leaves = P.n_leaves;
+  void* args[] = {&CA, &n_items, &entries, &n_leaves};  // (the global-memory kernels take the first alone)
+  HIPCHK(hipLaunchKernel(fn, dim3(P.info.grid), dim3(P.info.block), args, (size_t)lds, st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_done, st));
+  c->last_feature = P.info;
+  if (ch) {
+    HIPCHK(hipEventRecord(c->ev_fc, st));
+    c->fc_made = true;
+    c->fc_samples = (int64_t)p->width * p->height * n;
+  }
+  return RT_OK;
+}
+
+// rt_ids_matte*'s and rt_ids_preview*'s argument checks, before any HIP call; the ctx last.
+int ids_resolve_check(const char* what, const rt_ctx* c, int64_t pixels, bool pointers, const uint32_t* ids, int n_ids,
+                      bool list) {
+  const char* bad = list ? rt::ids_list_error(ids, n_ids) : nullptr;
+  if (!bad && !pointers) bad = "null records or no output";
+  if (!bad && (pixels < 1 || pixels >= (1ll << 32))) bad = "pixels must be in 1..2^32-1";
+  if (!bad && !c) bad = "null ctx";
+  return bad ? invalid(std::string(what) + ": " + bad) : RT_OK;
+}
+
+// A matte (ids non-null) or a preview queued on `st` over device pointers, in the ctx's launch order like a
+// feature pass. The list goes through the ctx's staging buffer, which the ordering keeps for this call until its
+// kernel has run; the copy from the caller's pageable array has left it when hipMemcpyAsync returns.
+int ids_resolve_queue(rt_ctx* c, const rt_id_record* d_recs, int64_t pixels, const uint32_t* ids, int n_ids,
+                      double* d_cov, uint8_t* d_u8, hipStream_t st) {
+  int rc;
+  if (ids && (rc = grow(c, c->id_list, sizeof(uint32_t) * RT_ID_MATTE_MAX))) return rc;
+  if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
+  c->last_stream = st;
+  int e;
+  if (ids) {
+    HIPCHK(hipMemcpyAsync(c->id_list.p, ids, sizeof(uint32_t) * (size_t)n_ids, hipMemcpyHostToDevice, st));
+    e = rt::ids_matte_launch(d_recs, pixels, (const uint32_t*)c->id_list.p, n_ids, d_cov, d_u8, (void*)st);
+  } else {
+    e = rt::ids_preview_launch(d_recs, pixels, d_u8, (void*)st);
+  }
+  if (e) return hip_fail((hipError_t)e, "rt_ids resolve launch");
+  HIPCHK(hipEventRecord(c->ev_done, st));
+  return RT_OK;
+}
+
+// The blocking variants: the records up, the kernel on the ctx's stream, the outputs back, in the ctx's buffers.
+int ids_resolve_blocking(rt_ctx* c, const rt_id_record* recs, int64_t pixels, const uint32_t* ids, int n_ids,
+                         double* out_cov, uint8_t* out_u8) {
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  const size_t npx = (size_t)pixels, u8_bytes = ids ? npx : 3 * npx;
+  int rc;
+  if ((rc = grow(c, c->id_recs, sizeof(rt_id_record) * npx)) || (out_cov && (rc = grow(c, c->id_cov, sizeof(double) * npx))) ||
+      (out_u8 && (rc = grow(c, c->id_u8, u8_bytes))))
+    return rc;
+  HIPCHK(hipMemcpy(c->id_recs.p, recs, sizeof(rt_id_record) * npx, hipMemcpyHostToDevice));
+  rc = ids_resolve_queue(c, (const rt_id_record*)c->id_recs.p, pixels, ids, n_ids, out_cov ? (double*)c->id_cov.p : nullptr,
+                         out_u8 ? (uint8_t*)c->id_u8.p : nullptr, c->stream);
+  c->id_allocs = c->allocs;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (rc) return rc;
+  if (out_cov) HIPCHK(hipMemcpy(out_cov, c->id_cov.p, sizeof(double) * npx, hipMemcpyDeviceToHost));
+  if (out_u8) HIPCHK(hipMemcpy(out_u8, c->id_u8.p, u8_bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+}  // namespace
+
+int rt_render_ids_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                        int first_sample, int n_samples, int accumulate, rt_id_record* d_records, void* stream) {
+  int rc = ids_check(c, cam, p, chain, first_sample, n_samples, d_records);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  rc = launch_ids(c, cam, p, chain, first_sample, n_samples, accumulate, d_records, (hipStream_t)stream);
+  c->id_allocs = c->allocs;
+  return rc;
+}
+
+int rt_render_ids(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                  int first_sample, int n_samples, int accumulate, rt_id_record* records) {
+  int rc = ids_check(c, cam, p, chain, first_sample, n_samples, records);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  const size_t bytes = sizeof(rt_id_record) * (size_t)p->width * (size_t)p->height;
+  if ((rc = grow(c, c->id_recs, bytes))) return rc;
+  if (accumulate) HIPCHK(hipMemcpy(c->id_recs.p, records, bytes, hipMemcpyHostToDevice));
+  rc = launch_ids(c, cam, p, chain, first_sample, n_samples, accumulate, (rt_id_record*)c->id_recs.p, c->stream);
+  c->id_allocs = c->allocs;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(records, c->id_recs.p, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_ids_matte_async(rt_ctx* c, const rt_id_record* d_recs, int64_t pixels, const uint32_t* ids, int n_ids,
+                       double* d_out_cov, uint8_t* d_out_u8, void* stream) {
+  int rc = ids_resolve_check("rt_ids_matte_async", c, pixels, d_recs && (d_out_cov || d_out_u8), ids, n_ids, true);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  rc = ids_resolve_queue(c, d_recs, pixels, ids, n_ids, d_out_cov, d_out_u8, (hipStream_t)stream);
+  c->id_allocs = c->allocs;
+  return rc;
+}
+
+int rt_ids_matte(rt_ctx* c, const rt_id_record* recs, int64_t pixels, const uint32_t* ids, int n_ids, double* out_cov,
+                 uint8_t* out_u8) {
+  int rc = ids_resolve_check("rt_ids_matte", c, pixels, recs && (out_cov || out_u8), ids, n_ids, true);
+  return rc ? rc : ids_resolve_blocking(c, recs, pixels, ids, n_ids, out_cov, out_u8);
+}
+
+int rt_ids_preview_async(rt_ctx* c, const rt_id_record* d_recs, int64_t pixels, uint8_t* d_out_rgb8, void* stream) {
+  int rc = ids_resolve_check("rt_ids_preview_async", c, pixels, d_recs && d_out_rgb8, nullptr, 0, false);
+  if (rc) return rc;
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  rc = ids_resolve_queue(c, d_recs, pixels, nullptr, 0, nullptr, d_out_rgb8, (hipStream_t)stream);
+  c->id_allocs = c->allocs;
+  return rc;
+}
+
+int rt_ids_preview(rt_ctx* c, const rt_id_record* recs, int64_t pixels, uint8_t* out_rgb8) {
+  int rc = ids_resolve_check("rt_ids_preview", c, pixels, recs && out_rgb8, nullptr, 0, false);
+  return rc ? rc : ids_resolve_blocking(c, recs, pixels, nullptr, 0, nullptr, out_rgb8);
+}
+
+// Internal (rt_internal.h): hipMalloc calls the ctx's last rt_render_ids*, rt_ids_matte* or rt_ids_preview* made.
+int rt_internal_ids_allocs(rt_ctx* c) { return c ? c->id_allocs : -1; }
+
+// Internal (rt_internal.h; no device needed): the plan an id pass would launch with.
+int rt_internal_ids_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p,
+                         const rt_feature_chain* chain, rt_launch_info* out, int32_t* out_extra) {
+  const int rc = chain ? chain_check(chain) : RT_OK;
+  return rc ? rc : features_plan(desc, upload_flags, cu_count, p, true, out, out_extra);
 }
 
 int rt_last_feature_launch(rt_ctx* c, rt_launch_info* out) {

@@ -194,6 +194,18 @@ class rt_feature_chain_stats(C.Structure):
                 ("ended_cap", C.c_int64), ("bounces", C.c_int64)]
 
 
+RT_ID_SLOTS, RT_ID_MISS, RT_ID_MATTE_MAX = 7, 0xFFFFFFFF, 1024
+
+
+class rt_id_record(C.Structure):
+    _fields_ = [("id", C.c_uint32 * RT_ID_SLOTS), ("count", C.c_uint32 * RT_ID_SLOTS), ("other", C.c_uint32),
+                ("samples", C.c_uint32)]
+
+
+# rt_id_record (rt.h) as a numpy structured dtype: one record per pixel of a material-ID pass
+ID_DTYPE = np.dtype([("id", "<u4", (RT_ID_SLOTS,)), ("count", "<u4", (RT_ID_SLOTS,)), ("other", "<u4"),
+                     ("samples", "<u4")])
+assert C.sizeof(rt_id_record) == 64 and ID_DTYPE.itemsize == 64
 assert C.sizeof(rt_feature_chain) == 16 and C.sizeof(rt_feature_chain_stats) == 40
 assert C.sizeof(rt_denoise_params) == 56 and C.sizeof(rt_denoise_stats) == 40 and C.sizeof(rt_denoise_info) == 16
 assert C.sizeof(rt_frame_ckpt_desc) == 344
@@ -228,6 +240,8 @@ EXPORTED = [
     "rt_render_features", "rt_render_features_async", "rt_last_feature_launch", "rt_features_resolve",
     "rt_denoise_host", "rt_denoise", "rt_denoise_async", "rt_last_denoise", "rt_frame_denoise",
     "rt_render_features_chain", "rt_render_features_chain_async", "rt_last_feature_chain",
+    "rt_render_ids", "rt_render_ids_async", "rt_ids_fold_host", "rt_ids_resolve", "rt_ids_matte_host", "rt_ids_matte",
+    "rt_ids_matte_async", "rt_ids_preview_host", "rt_ids_preview", "rt_ids_preview_async",
 ]
 
 # The feature-guided denoiser's flags (rt.h)
@@ -372,6 +386,20 @@ def lib() -> C.CDLL:
             "rt_render_features_chain_async": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(rt_feature_chain),
                                                    I, I, I, C.c_void_p, C.c_void_p]),
             "rt_last_feature_chain": (I, [C.c_void_p, P(rt_feature_chain_stats)]),
+            "rt_render_ids": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(rt_feature_chain), I, I, I,
+                                  C.c_void_p]),
+            "rt_render_ids_async": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(rt_feature_chain), I, I, I,
+                                        C.c_void_p, C.c_void_p]),
+            "rt_ids_fold_host": (I, [C.c_void_p, P(C.c_uint32), C.c_int64]),
+            "rt_ids_resolve": (I, [C.c_void_p, C.c_int64, P(C.c_uint32), P(D), P(D)]),
+            "rt_ids_matte_host": (I, [C.c_void_p, C.c_int64, P(C.c_uint32), I, P(D), P(C.c_uint8)]),
+            "rt_ids_matte": (I, [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_uint32), I, P(D), P(C.c_uint8)]),
+            "rt_ids_matte_async": (I, [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_uint32), I, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+            "rt_ids_preview_host": (I, [C.c_void_p, C.c_int64, P(C.c_uint8)]),
+            "rt_ids_preview": (I, [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_uint8)]),
+            "rt_ids_preview_async": (I, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+            "rt_internal_ids_allocs": (I, [C.c_void_p]),
             "rt_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8), P(rt_denoise_stats)]),
             "rt_internal_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8),
                                              P(rt_denoise_stats), P(D)]),
@@ -890,6 +918,74 @@ class Context:
         _check(lib().rt_last_feature_launch(self._h, C.byref(info)), "rt_last_feature_launch")
         return {k: getattr(info, k) for k, _ in rt_launch_info._fields_}
 
+    def render_ids(self, cam: rt_camera, params: rt_render_params, first_sample: int = 0,
+                   n_samples: Optional[int] = None, chain: Optional["rt_feature_chain"] = None,
+                   accumulate: Optional[np.ndarray] = None) -> np.ndarray:
+        """rt_render_ids: the material-ID records of samples first_sample .. first_sample + n_samples - 1 (default:
+        params.spp samples), (H, W) of ID_DTYPE: per pixel up to 7 (id, count) slots in order of first appearance,
+        `other` and `samples` (`resolve_ids`, `id_matte` and `id_preview` make images of them). `chain`
+        (`make_feature_chain`): the material at the end of each sample's specular chain instead of the first hit's.
+        `accumulate` ((H, W) of ID_DTYPE, C order) is folded onto in place and returned. Blocking."""
+        W, H = params.width, params.height
+        n = params.spp if n_samples is None else n_samples
+        if accumulate is None:
+            recs = np.zeros((H, W), dtype=ID_DTYPE)
+        else:
+            recs = accumulate
+            if recs.dtype != ID_DTYPE or recs.shape != (H, W) or not recs.flags.c_contiguous:
+                raise RTError("render_ids: `accumulate` must be a C-contiguous (H, W) array of ID_DTYPE")
+        _check(lib().rt_render_ids(self._h, C.byref(cam), C.byref(params), C.byref(chain) if chain is not None else None,
+                                   int(first_sample), int(n), int(accumulate is not None), C.c_void_p(recs.ctypes.data)),
+               "rt_render_ids")
+        return recs
+
+    def render_ids_async(self, cam, params, d_records: int, first_sample: int = 0, n_samples: Optional[int] = None,
+                         chain: Optional["rt_feature_chain"] = None, accumulate: bool = False, stream: int = 0):
+        """rt_render_ids_async: the same pass queued on `stream` into device memory (H*W records of 64 bytes)."""
+        n = params.spp if n_samples is None else n_samples
+        _check(lib().rt_render_ids_async(self._h, C.byref(cam), C.byref(params),
+                                         C.byref(chain) if chain is not None else None, int(first_sample), int(n),
+                                         int(accumulate), C.c_void_p(d_records), C.c_void_p(stream or None)),
+               "rt_render_ids_async")
+
+    def id_matte(self, records, ids, pixels: Optional[int] = None, d_out_cov: int = 0, d_out_u8: int = 0,
+                 stream: int = 0):
+        """rt_ids_matte: `id_matte` on this ctx's device, bit for bit: (coverage, bytes) of host records, blocking.
+        With a device pointer (an int) as `records`: rt_ids_matte_async over `pixels` records into the device
+        arrays d_out_cov (doubles) and / or d_out_u8, queued on `stream`; returns None. Needs no scene."""
+        lst = _id_list(ids)
+        lp = lst.ctypes.data_as(C.POINTER(C.c_uint32))
+        if isinstance(records, (int, np.integer)):
+            _check(lib().rt_ids_matte_async(self._h, C.c_void_p(int(records)), int(pixels or 0), lp, len(lst),
+                                            C.c_void_p(d_out_cov or None), C.c_void_p(d_out_u8 or None),
+                                            C.c_void_p(stream or None)), "rt_ids_matte_async")
+            return None
+        r = _id_records(records)
+        cov, u8 = np.zeros(r.shape), np.zeros(r.shape, dtype=np.uint8)
+        _check(lib().rt_ids_matte(self._h, C.c_void_p(r.ctypes.data), r.size, lp, len(lst),
+                                  cov.ctypes.data_as(C.POINTER(C.c_double)), u8.ctypes.data_as(C.POINTER(C.c_uint8))),
+               "rt_ids_matte")
+        return cov, u8
+
+    def id_preview(self, records, pixels: Optional[int] = None, d_out_rgb8: int = 0, stream: int = 0):
+        """rt_ids_preview: `id_preview` on this ctx's device, bit for bit, blocking; with a device pointer as
+        `records`, rt_ids_preview_async over `pixels` records into d_out_rgb8 on `stream` (returns None)."""
+        if isinstance(records, (int, np.integer)):
+            _check(lib().rt_ids_preview_async(self._h, C.c_void_p(int(records)), int(pixels or 0),
+                                              C.c_void_p(d_out_rgb8 or None), C.c_void_p(stream or None)),
+                   "rt_ids_preview_async")
+            return None
+        r = _id_records(records)
+        rgb = np.zeros(r.shape + (3,), dtype=np.uint8)
+        _check(lib().rt_ids_preview(self._h, C.c_void_p(r.ctypes.data), r.size, rgb.ctypes.data_as(C.POINTER(C.c_uint8))),
+               "rt_ids_preview")
+        return rgb
+
+    def last_id_allocs(self) -> int:
+        """Device allocations the ctx's last render_ids, id_matte or id_preview call made (0 on a repeat of one
+        size)."""
+        return int(lib().rt_internal_ids_allocs(self._h))
+
     def denoise(self, params: "rt_denoise_params", color, se, feature_sums, rgb: bool = True):
         """rt_denoise: `denoise_host` on this ctx's device, bit for bit; host arrays, blocking. Needs no scene."""
         return _denoise_call(lib().rt_denoise, "rt_denoise", (self._h,), params, color, se, feature_sums, rgb)
@@ -994,6 +1090,64 @@ def resolve_features(sums: np.ndarray, n_samples: int) -> dict:
                                      out["coverage"].ctypes.data_as(P(C.c_double)),
                                      out["albedo_rgb8"].ctypes.data_as(P(C.c_uint8))), "rt_features_resolve")
     return out
+
+
+def _id_records(records) -> np.ndarray:
+    r = np.ascontiguousarray(records)
+    if r.dtype != ID_DTYPE or r.size < 1:
+        raise RTError("material-ID records must be a non-empty array of ID_DTYPE")
+    return r
+
+
+def _id_list(ids) -> np.ndarray:
+    """A matte's id list as the C calls take it (they check its order and length)."""
+    return np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+
+
+def fold_ids(record=None, ids=()) -> np.ndarray:
+    """rt_ids_fold_host: the sample ids `ids`, in order, folded into a copy of `record` (a 0-d ID_DTYPE array or
+    record; None: a zero record) by rt.h's rule; returns the new record as a 0-d array."""
+    rec = np.zeros((), dtype=ID_DTYPE)
+    if record is not None:
+        rec[()] = np.asarray(record, dtype=ID_DTYPE).reshape(())[()]
+    lst = _id_list(ids)
+    _check(lib().rt_ids_fold_host(C.c_void_p(rec.ctypes.data), lst.ctypes.data_as(C.POINTER(C.c_uint32)), len(lst)),
+           "rt_ids_fold_host")
+    return rec
+
+
+def resolve_ids(records) -> dict:
+    """rt_ids_resolve: per pixel the slots ranked by count (descending, ties by id ascending): rank_ids (..., 7)
+    (RT_ID_MISS in a free slot), rank_coverage (..., 7) = count / samples, other_coverage (...), and samples (...)."""
+    r = _id_records(records)
+    out = {"rank_ids": np.zeros(r.shape + (RT_ID_SLOTS,), dtype=np.uint32),
+           "rank_coverage": np.zeros(r.shape + (RT_ID_SLOTS,)), "other_coverage": np.zeros(r.shape),
+           "samples": r["samples"].copy()}
+    _check(lib().rt_ids_resolve(C.c_void_p(r.ctypes.data), r.size, out["rank_ids"].ctypes.data_as(C.POINTER(C.c_uint32)),
+                                out["rank_coverage"].ctypes.data_as(C.POINTER(C.c_double)),
+                                out["other_coverage"].ctypes.data_as(C.POINTER(C.c_double))), "rt_ids_resolve")
+    return out
+
+
+def id_matte(records, ids) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_ids_matte_host: the matte of the materials `ids` (strictly ascending, 1..1024 of them; RT_ID_MISS: the
+    sky): (coverage, bytes), coverage = the listed slots' counts / samples, byte = (uint8)(coverage * 255 + 0.5)."""
+    r, lst = _id_records(records), _id_list(ids)
+    cov, u8 = np.zeros(r.shape), np.zeros(r.shape, dtype=np.uint8)
+    _check(lib().rt_ids_matte_host(C.c_void_p(r.ctypes.data), r.size, lst.ctypes.data_as(C.POINTER(C.c_uint32)), len(lst),
+                                   cov.ctypes.data_as(C.POINTER(C.c_double)), u8.ctypes.data_as(C.POINTER(C.c_uint8))),
+           "rt_ids_matte_host")
+    return cov, u8
+
+
+def id_preview(records) -> np.ndarray:
+    """rt_ids_preview_host: a false-colour image (..., 3) uint8 of the records: each slot's hashed colour weighted
+    by its coverage."""
+    r = _id_records(records)
+    rgb = np.zeros(r.shape + (3,), dtype=np.uint8)
+    _check(lib().rt_ids_preview_host(C.c_void_p(r.ctypes.data), r.size, rgb.ctypes.data_as(C.POINTER(C.c_uint8))),
+           "rt_ids_preview_host")
+    return rgb
 
 
 DENOISE_STATS_FIELDS = ("pixels", "invalid_in", "invalid_out", "filled", "kernel_ms")
