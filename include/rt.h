@@ -230,7 +230,10 @@ static inline int rt_sample_chunk(int64_t pixels, int spp) {
                                Output-identical; off by default. */
 #define RT_FLAG_REFERENCE_CULL 2u /* cull BVH boxes with the reference's per-axis test only
                                (src/Lib.hs:798-814). Default: that test AND the joint slab test,
-                               which only prunes boxes that cannot hold a hit. A world
+                               which prunes only hits that the reference takes by rounding, where the
+                               exact ray misses the leaf or touches its rim: a sphere reports hits up to
+                               about |o - c|^2 * 2^-52 / r outside itself for a tangent ray, 2^4 radii
+                               of a unit sphere from 2^28 away ("Far origins"). A world
                                with a finite BVH box coordinate beyond 2^100 always takes this flag. */
 #define RT_FLAG_NAN_ZERO 4u /* tiers A and B, parity diagnostic (NOT the reference's semantics): a sample
                                contribution channel that is NaN is added as 0, so that the finite

@@ -242,9 +242,13 @@ bool flat_box(const std::vector<rt_node>& nodes, int id, Box* out) {
       // (src/Lib.hs:732-761): the corners and points extrapolated a whole box extent beyond them, a box
       // 3x as wide per axis. The re-bounded trees' boxes only cull (ties are redone on the caller's tree,
       // which keeps the reference's boxes), so they bound the child by its 8 corners (rotation is
-      // linear), widened by 2^-30 of the magnitudes against rounding (round 6: the 1000-sphere frame of
+      // linear), widened by 2^-19 of the magnitudes against rounding (round 6: the 1000-sphere frame of
       // next_week_final was opened by every ray through its 27-times-larger box). RTAMD_TIGHT_ROTATE=0
-      // keeps the reference's box.
+      // keeps the reference's box. The leaf is hit through unRotatePoint(ray), whose rounding grows with
+      // |o|, not with the box, so no static pad covers every origin: 2^-19 is 4x the smallest power of two
+      // at which the host model of tests/far_rays.py culls no reference hit on a rotated leaf that the
+      // reference's box keeps, for origins up to 2^36 box sizes away ("Far origins and
+      // tangent rays"; it was 2^-30, which lost such hits from 2^28 on).
       static const bool tight = !(std::getenv("RTAMD_TIGHT_ROTATE") && std::getenv("RTAMD_TIGHT_ROTATE")[0] == '0');
       for (int idx = 26; idx >= 0; --idx) {
         const double i = idx / 9, j = (idx / 3) % 3, k = idx % 3;
@@ -258,7 +262,7 @@ bool flat_box(const std::vector<rt_node>& nodes, int id, Box* out) {
         for (int a = 0; a < 3; ++a) { mn[a] = gmin(q[a], mn[a]); mx[a] = gmax(q[a], mx[a]); }
       }
       for (int a = 0; a < 3; ++a) {
-        const double pad = tight ? 0x1p-30 * (std::fabs(mn[a]) + std::fabs(mx[a]) + 1.0) : 0.0;
+        const double pad = tight ? 0x1p-19 * (std::fabs(mn[a]) + std::fabs(mx[a]) + 1.0) : 0.0;
         out->mn[a] = mn[a] - pad;
         out->mx[a] = mx[a] + pad;
       }

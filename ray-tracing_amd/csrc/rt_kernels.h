@@ -526,7 +526,7 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
     // this walk as the reference does (once). (NaN-t hits come from the Lambertian quirk's +x ray in a
     // box top's plane, whose pdf is 0 / 0: DESIGN.md §4.3. A walking path's throughput is never NaN in
     // every channel: such a path ends where it is shaded, below.)
-    if (ready && (t.tie || (kRefMixed<F> && t.lite)) && !t.redo) {
+    if (ready && (((t.tie || (kRefMixed<F> && t.lite)) && !t.redo) || redo_again<F>(t))) {
       if constexpr ((F & F_COUNT) != 0) ++cnt.ties;
       trav_redo<F>(t, L.S.world_ref, INFINITY);
       // (the redo's binary box tests need 1/d: recomputed here, the same values, so that the 4-wide
@@ -536,8 +536,10 @@ __device__ __forceinline__ void philox_loop2(const RenderArgs& A, const LaunchCo
         // The redo runs to its end here, a divergent loop over the flagged lanes, and the lane is shaded below
         // in this same iteration (`ready` stays set; t.redo keeps it from being redone): the 4-wide step loop then
         // holds no binary step and no lane in a redo. Ties are rare (C2 none); only test worlds have many.
-        while (trav_step<F, true>(S, t, kEps, stk, stride, joint, cnt, g, side)) {
-        }
+        do {
+          while (trav_step<F, true>(S, t, kEps, stk, stride, joint, cnt, g, side)) {
+          }
+        } while (redo_again<F>(t) && (trav_redo<F>(t, L.S.world_ref, INFINITY), true));
         t.node = kNone;  // (with pend = -1: the walk is over, in walk_until's terms too)
       } else {
         ready = false;
@@ -1241,8 +1243,10 @@ __global__ void __launch_bounds__(RT_BLOCK) closest_hits(Scene S, const double* 
     if (t.tie || (kRefMixed<F> && t.lite)) {
       trav_redo<F>(t, S.world_ref, tmax);
       if constexpr (kNoInv<F>) t.ray = prep(plain(t.ray));  // (the redo's binary box tests need 1/d)
-      while (trav_step<F>(S, t, tmin, stk, RT_BLOCK, joint != 0, cnt, g, side)) {
-      }
+      do {
+        while (trav_step<F>(S, t, tmin, stk, RT_BLOCK, joint != 0, cnt, g, side)) {
+        }
+      } while (redo_again<F>(t) && (trav_redo<F>(t, S.world_ref, tmax), true));
     }
     got = trav_finish<F>(S, t, r, tmin, h, side);
   }
@@ -1294,8 +1298,10 @@ __device__ __forceinline__ bool first_hit(const Scene& S, const Ray& r, RngPhilo
     if (t.tie || (kRefMixed<F> && t.lite)) {
       trav_redo<F>(t, S.world_ref, INFINITY);
       if constexpr (kNoInv<F>) t.ray = prep(plain(t.ray));  // (the redo's binary box tests need 1/d)
-      while (trav_step<F>(S, t, kEps, stk, stride, joint, cnt, g, side)) {
-      }
+      do {
+        while (trav_step<F>(S, t, kEps, stk, stride, joint, cnt, g, side)) {
+        }
+      } while (redo_again<F>(t) && (trav_redo<F>(t, S.world_ref, INFINITY), true));
     }
     return trav_finish<F>(S, t, r, kEps, h, side);
   }

@@ -107,8 +107,12 @@ __device__ __forceinline__ bool q_ok(double a, double q) { return in_range(a) & 
 // with the reference's quotients (bit-exact) and GHC max/min. The reference never intersects the
 // three axis intervals; with `joint` the box must ALSO pass the joint slab test (max of the axis
 // lower bounds < min of the upper bounds). That accepts a subset of the reference's boxes, so it
-// only prunes subtrees; what it prunes cannot hold a hit in [t_min, t_max] except exactly on a box
-// face (measure zero; tests/test_gpu_parity.py checks closest hits bit for bit).
+// only prunes subtrees. What it prunes are hits that the reference takes by rounding: the exact ray
+// misses the leaf, or meets it within a few ulps of |o| of its rim (a box face; measure zero for
+// origins near the world, tests/test_gpu_parity.py checks closest hits bit for bit). The share grows
+// with |o|: for a tangent ray the sphere test, whose c = |o - c|^2 - r^2 loses r^2, reports hits up
+// to about |o - c|^2 * 2^-52 / r outside the sphere, which no box of the sphere holds. Measured per
+// origin distance in tests/test_gpu_far_rays.py ("Far origins and tangent rays").
 __device__ __forceinline__ bool box_hit_exact(const double* f, const RayX& r, double t_min, double t_max, bool joint) {
   bool ok = true;
   double lmax = t_min, hmin = t_max;
@@ -829,6 +833,16 @@ __device__ __forceinline__ void trav_redo(Trav& t, int root, double t_max) {
   const double up = __longlong_as_double(__double_as_longlong(c) + (c > 0 ? 1 : -1));
   trav_restart_ref(t, root, up < t_max ? up : t_max, true);  // (t* == t_max: the reference's own bound)
   t.lite = true;
+}
+// A redo bounded by nextafter(t*) that ends without a hit has to be done again in full. It relies on the
+// tied leaves' hits lying inside their boxes in the caller's tree. For a far origin they need not: the sphere
+// test, whose c = |o - c|^2 - r^2 loses r^2, reports hits many radii outside the sphere, several spheres at
+// one and the same t, which the re-bounded tree's walk can reach and the reference's boxes cull. The
+// reference's closest hit then lies beyond t* (tests/test_gpu_far_rays.py). trav_redo sees `lite` set and
+// restarts unbounded, which clears it: at most one more walk.
+template <unsigned F>
+__device__ __forceinline__ bool redo_again(const Trav& t) {
+  return kRefMixed<F> && t.redo && t.lite && t.best_node < 0;
 }
 
 // Leaf of the resumable walk (a primitive, or an instance chain ending in one). Leaves are tested
