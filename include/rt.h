@@ -705,6 +705,54 @@ int rt_ids_preview(rt_ctx* ctx, const rt_id_record* recs, int64_t pixels, uint8_
 int rt_ids_preview_async(rt_ctx* ctx, const rt_id_record* d_recs, int64_t pixels, uint8_t* d_out_rgb8, void* stream);
 
 /*
+ * Sharded feature and ID passes: the three passes above over one shard's slab, and the merge of the shards' slabs.
+ * The image-order entries above keep rejecting shard_count > 1; these are the per-device building blocks, as
+ * rt_render_shard_async and rt_assemble_async are for the render. Tier B only.
+ *
+ * Geometry. The shard is (tile, shard_rank, shard_count) of `p`, with the geometry of rt_shard_geometry
+ * (shard_count 0 means 1). The slab holds slab_pixels records of 64 bytes (RT_FEATURE_DOUBLES doubles, or one
+ * rt_id_record) in slab order: tile-major over the shard's tiles r, r+N, r+2N, ...; inside a tile its 8x8 pixel
+ * blocks row-major; inside a block (row & 7) * 8 + (px & 7). With lt the tile's index in the shard, bpr = tile / 8 and
+ * (bx, by) the pixel's block inside the tile,
+ *     slot = lt * tile * tile + (by * bpr + bx) * 64 + (row & 7) * 8 + (px & 7),
+ * the slot rt_assemble_async reads. slot >> 6 numbers the slab's blocks: a wave folds one block and stores its 64
+ * records as one contiguous 4 KB run.
+ * Slot content. The slot of an image pixel holds, byte for byte, what the image-order pass (rt_render_features_async,
+ * rt_render_features_chain_async, rt_render_ids_async) writes for that pixel with the same seed, flags, chain,
+ * sample range and `accumulate`: a sample's stream is keyed by pid = row*W + px and the sample index, so which
+ * shard folds a pixel does not show. Accumulating reads the slot first.
+ * Padding. Slots of no image pixel (tile overhang, tiles past the image's last) are neither read nor written, with
+ * `accumulate` too. A shard that owns no tile returns RT_OK and writes nothing. shard_count == 1 is legal: the
+ * one-shard slab.
+ *
+ * rt_render_features_shard_async  a first-hit pass (chain NULL) or a specular-chain pass over the slab, queued on
+ *                                 `stream` into device memory on the ctx's device.
+ * rt_render_ids_shard_async       the material-ID pass over the slab (chain may be NULL).
+ * Ordering is the feature passes': after the ctx's previous tier-B launch and before its next, whichever streams they
+ * use; renders around a slab pass keep their bytes. The kernel forms are the ones the image-order pass of the same
+ * world takes. rt_last_feature_launch reports the form, with work_items = the shard's tiles inside the image x
+ * (tile/8)^2 (for one shard at tile 8, the image-order pass's count; 0 for a shard that owns no tile). After a chain or
+ * ID-chain pass rt_last_feature_chain reports this shard's counts, samples = the shard's image pixels x n_samples;
+ * added over the shards they are the image-order pass's counts.
+ * RT_E_INVALID, before any HIP call: everything the image-order entry rejects other than shard_count > 1; what
+ * rt_shard_geometry rejects of tile, shard_rank and shard_count; a slab of 2^32 slots or more; a null slab pointer.
+ * RT_E_STATE without a scene. A multi-device ctx runs the pass on its first device.
+ *
+ * rt_assemble_records_async  d_slabs: shard_count slabs concatenated rank-major; d_image: [H][W] records on the ctx's
+ *                            device. A pure byte move, for doubles and ID records alike, queued on `stream`; it reads no
+ *                            padding slot. Needs no scene. Of `p` it reads width, height, tile and shard_count.
+ * rt_assemble_records_host   the same on the host, no device.
+ */
+int rt_render_features_shard_async(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p,
+                                   const rt_feature_chain* chain, int first_sample, int n_samples, int accumulate,
+                                   double* d_slab_sums, void* stream);
+int rt_render_ids_shard_async(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p,
+                              const rt_feature_chain* chain, int first_sample, int n_samples, int accumulate,
+                              rt_id_record* d_slab_records, void* stream);
+int rt_assemble_records_async(rt_ctx* ctx, const rt_render_params* p, const void* d_slabs, void* d_image, void* stream);
+int rt_assemble_records_host(const rt_render_params* p, const void* slabs, void* image);
+
+/*
  * Feature-guided denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with SVGF-style variance
  * guidance over a linear image, its per-pixel standard error (optional) and the feature sums of a feature pass
  * (above). Tier-independent; every array is in image order (row 0 = top). fp64 throughout, no contraction, only

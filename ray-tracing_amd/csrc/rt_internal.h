@@ -91,6 +91,13 @@ extern "C" int rt_internal_features_chain_plan(const rt_scene_desc* desc, uint32
                                                const rt_render_params* p, const rt_feature_chain* chain,
                                                rt_launch_info* out, int32_t* out_extra);
 
+// The same for a pass over a shard's slab (rt_render_features_shard_async, rt_render_ids_shard_async): the shard is
+// (p->tile, p->shard_rank, p->shard_count); `chain` != 0: the chain passes' plan (an ID pass's too). The forms are
+// the image-order pass's, work_items the shard's tiles inside the image x (tile / 8)^2 (0: it owns none).
+extern "C" int rt_internal_features_shard_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count,
+                                               const rt_render_params* p, int chain, rt_launch_info* out,
+                                               int32_t* out_extra);
+
 // The same for a material-ID pass (rt_render_ids; `chain` may be null): the chain pass's plan, launched with
 // rt_k_ids.hip's kernels. And the hipMalloc calls the ctx's last rt_render_ids*, rt_ids_matte* or rt_ids_preview*
 // call made (-1: null ctx), for the tests: a repeat of one size makes none.

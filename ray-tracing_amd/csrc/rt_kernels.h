@@ -26,28 +26,7 @@ using namespace rtd;
 
 namespace {
 
-// Unsigned 32-bit division by an invariant divisor d >= 1 (Granlund & Montgomery): with
-// l = ceil(log2 d) and m = floor(2^32 (2^l - d) / d) + 1, n / d = (t + ((n - t) >> s1)) >> s2 for
-// every 32-bit n, t = umulhi(m, n), s1 = min(l, 1), s2 = max(l - 1, 0). One multiply and a few
-// shifts instead of the software division a `/` on the device becomes.
-struct UDiv {
-  uint32_t m;
-  int s1, s2;
-};
-inline UDiv make_udiv(uint32_t d) {
-  int l = 0;
-  while ((1ull << l) < d) ++l;
-  const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
-  return UDiv{(uint32_t)m, l < 1 ? l : 1, l > 1 ? l - 1 : 0};
-}
-__host__ __device__ __forceinline__ uint32_t udiv(uint32_t n, UDiv d) {
-#ifdef __HIP_DEVICE_COMPILE__
-  const uint32_t t = __umulhi(d.m, n);
-#else  // (the host evaluates the work decomposition for the launch-geometry check)
-  const uint32_t t = (uint32_t)(((uint64_t)d.m * n) >> 32);
-#endif
-  return (t + ((n - t) >> d.s1)) >> d.s2;
-}
+// (UDiv, make_udiv, udiv: rt_layout.h, with the record slab's block map that divides with them)
 
 // The launch's constants: everything a launch passes to its kernels. The small kernels (combine_chunks,
 // tail_combine) and tier A take it by value, and so do a progressive frame's frame_* helpers, which read the frame
@@ -137,7 +116,9 @@ __global__ void __launch_bounds__(64) launch_setup(LaunchConst L, LaunchConst* d
 }
 
 // Slab pixel index -> image pixel (tile-major, 8x8 blocks inside a tile). Slab indices are < 2^32
-// (plan_launch checks).
+// (plan_launch checks). The same map is stated twice more: `assemble` below is its inverse (image pixel -> slot),
+// and rt_layout.h's slab_block is this function per 8x8 block for the record slabs of the feature and ID passes
+// (tests/c/shard_block_check.cpp holds slab_block to assemble's formula). A change to one is a change to all.
 __host__ __device__ __forceinline__ bool work_pixel(const LaunchConst& A, uint32_t w, int& px, int& row) {
   const uint32_t tp = (uint32_t)(A.tile * A.tile);
   const uint32_t lt = udiv(w, A.div_tp);
@@ -1311,8 +1292,12 @@ __device__ __forceinline__ bool first_hit(const Scene& S, const Ray& r, RngPhilo
 // order, into eight accumulators and stores them once (64 contiguous bytes). Blocks are claimed from the pass's
 // counter, one atomic per wave and block; which wave folds a pixel does not show in its sums. Lanes outside the
 // image idle through the block.
-template <unsigned F, bool PK, bool REC>
-__device__ __forceinline__ void features_loop(const FeatureArgs& A, const Scene& S, int* stk, int stride, int* side_p) {
+// SLAB (rt_kernels_shard.h's kernels): the pass over a shard's record slab. A claimed block is block b of the slab
+// (rt_layout.h slab_block gives its pixels, `G` the shard's geometry) and the lane's record lives at slot b * 64 +
+// lane instead of the pixel's place in the image: a wave's 64 stores are one contiguous 4 KB run.
+template <unsigned F, bool PK, bool REC, bool SLAB = false>
+__device__ __forceinline__ void features_loop(const FeatureArgs& A, const Scene& S, int* stk, int stride, int* side_p,
+                                              const SlabGeometry* G = nullptr) {
   const int lane = threadIdx.x & 63;
   const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
   Side side{side_p, stride};
@@ -1321,11 +1306,18 @@ __device__ __forceinline__ void features_loop(const FeatureArgs& A, const Scene&
     if (lane == 0) b = atomicAdd(A.counter, 1ull);
     b = __shfl(b, 0);
     if (b >= A.blocks_total) break;
-    const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
-    const int px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    int px, row;
+    if constexpr (SLAB) {
+      int px0 = A.W, row0 = A.H;  // (a block of a tile past the image's last, which the host never hands out: idles)
+      slab_block(*G, (uint32_t)b, px0, row0);
+      px = px0 + (lane & 7), row = row0 + (lane >> 3);
+    } else {
+      const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
+      px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    }
     if (px >= A.W || row >= A.H) continue;  // (idles until the wave's next claim)
     const uint32_t pid = (uint32_t)((long long)row * A.W + px);
-    double* q = A.sums + (size_t)pid * RT_FEATURE_DOUBLES;
+    double* q = A.sums + (SLAB ? (size_t)b * 64 + (size_t)lane : (size_t)pid) * RT_FEATURE_DOUBLES;
     double acc[RT_FEATURE_DOUBLES];
 #pragma unroll
     for (int k = 0; k < RT_FEATURE_DOUBLES; ++k) acc[k] = A.accumulate ? q[k] : 0.0;
@@ -1425,9 +1417,9 @@ struct FeatureChainArgs {
 // Not once per block: an `if (lane == 0) atomicAdd` at the bottom of the block loop sits next to the claim's
 // `if (lane == 0)` at its top, the compiler threads the one branch into the other, and the wave's lanes no longer
 // meet at the claim's __shfl: the lanes that skipped both read a stale block id and never leave the loop.
-template <unsigned F, bool PK, bool REC>
+template <unsigned F, bool PK, bool REC, bool SLAB = false>  // (SLAB: as features_loop)
 __device__ __forceinline__ void features_chain_loop(const FeatureChainArgs& C, const Scene& S, int* stk, int stride,
-                                                    int* side_p) {
+                                                    int* side_p, const SlabGeometry* G = nullptr) {
   const FeatureArgs& A = C.A;
   const int lane = threadIdx.x & 63;
   const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
@@ -1438,11 +1430,18 @@ __device__ __forceinline__ void features_chain_loop(const FeatureChainArgs& C, c
     if (lane == 0) b = atomicAdd(A.counter, 1ull);
     b = __shfl(b, 0);
     if (b >= A.blocks_total) break;
-    const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
-    const int px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    int px, row;
+    if constexpr (SLAB) {
+      int px0 = A.W, row0 = A.H;
+      slab_block(*G, (uint32_t)b, px0, row0);
+      px = px0 + (lane & 7), row = row0 + (lane >> 3);
+    } else {
+      const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
+      px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    }
     if (px < A.W && row < A.H) {  // (a lane outside the image idles until the wave's next claim)
       const uint32_t pid = (uint32_t)((long long)row * A.W + px);
-      double* q = A.sums + (size_t)pid * RT_FEATURE_DOUBLES;
+      double* q = A.sums + (SLAB ? (size_t)b * 64 + (size_t)lane : (size_t)pid) * RT_FEATURE_DOUBLES;
       double acc[RT_FEATURE_DOUBLES];
 #pragma unroll
       for (int k = 0; k < RT_FEATURE_DOUBLES; ++k) acc[k] = A.accumulate ? q[k] : 0.0;
@@ -1532,6 +1531,12 @@ __global__ void __launch_bounds__(WAVES * 256) render_features_chain_lds(Feature
 // A chain pass's arguments: A.sums is the pass's rt_id_record array (64 bytes per pixel, as a feature vector), a
 // pass without a chain has max_bounces = 0, and `counts` may be null (then nothing is counted).
 using IdArgs = FeatureChainArgs;
+// A slab pass's arguments (rt_kernels_shard.h's kernels), for all three passes: the chain pass's (a first-hit pass
+// reads C.A alone, an ID pass without a chain has max_bounces = 0 and null counts) and the shard's geometry.
+struct FeatureSlabArgs {
+  FeatureChainArgs C;
+  SlabGeometry G;
+};
 
 // features_chain_loop's nest (its comment says why it has this shape: ended lanes leave the chain loop and
 // reconverge, first_hit's ballot sees the lanes still in a chain, the counts go through wave_add after the block
@@ -1539,8 +1544,9 @@ using IdArgs = FeatureChainArgs;
 // RT_ID_MISS, folded into the lane's record by rt_ids.h's ids_fold_one, whose slots are compared and updated under
 // predicates and so stay in registers. No throughput, no path length, no albedo: the kernel has no texture code.
 // One loop for both modes: a pass without a chain runs it with max_bounces = 0, where no material is followed.
-template <unsigned F, bool PK, bool REC>
-__device__ __forceinline__ void ids_loop(const IdArgs& C, const Scene& S, int* stk, int stride, int* side_p) {
+template <unsigned F, bool PK, bool REC, bool SLAB = false>  // (SLAB: as features_loop)
+__device__ __forceinline__ void ids_loop(const IdArgs& C, const Scene& S, int* stk, int stride, int* side_p,
+                                         const SlabGeometry* G = nullptr) {
   const FeatureArgs& A = C.A;
   const int lane = threadIdx.x & 63;
   const bool joint = !(A.flags & RT_FLAG_REFERENCE_CULL);
@@ -1551,11 +1557,19 @@ __device__ __forceinline__ void ids_loop(const IdArgs& C, const Scene& S, int* s
     if (lane == 0) b = atomicAdd(A.counter, 1ull);
     b = __shfl(b, 0);
     if (b >= A.blocks_total) break;
-    const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
-    const int px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    int px, row;
+    if constexpr (SLAB) {
+      int px0 = A.W, row0 = A.H;
+      slab_block(*G, (uint32_t)b, px0, row0);
+      px = px0 + (lane & 7), row = row0 + (lane >> 3);
+    } else {
+      const uint32_t by = (uint32_t)b / (uint32_t)A.blocks_x, bx = (uint32_t)b - by * (uint32_t)A.blocks_x;
+      px = (int)(bx * 8u) + (lane & 7), row = (int)(by * 8u) + (lane >> 3);
+    }
     if (px < A.W && row < A.H) {  // (a lane outside the image idles until the wave's next claim)
       const uint32_t pid = (uint32_t)((long long)row * A.W + px);
-      uint4* q = reinterpret_cast<uint4*>(A.sums) + (size_t)pid * 4;  // (hipMalloc'd: 16-byte aligned records)
+      // (hipMalloc'd: 16-byte aligned records)
+      uint4* q = reinterpret_cast<uint4*>(A.sums) + (SLAB ? (size_t)b * 64 + (size_t)lane : (size_t)pid) * 4;
       static_assert(sizeof(rt_id_record) == 64 && sizeof(rt_id_record) == sizeof(double) * RT_FEATURE_DOUBLES, "rt.h");
       // the record, field by field in rt.h's order: id[7], count[7], other, samples
       const uint4 z = make_uint4(0u, 0u, 0u, 0u);
@@ -1820,4 +1834,10 @@ const void* philox_kernel_full_dark(const KernelForm& f);
 const void* features_kernel(const FeaturePlan& P);  // rt_k_features.hip (render_features / render_features_lds)
 const void* features_chain_kernel(const FeaturePlan& P);  // rt_k_features_chain.hip (the same forms, with a chain)
 const void* ids_kernel(const FeaturePlan& P);  // rt_k_ids.hip (the same forms: render_ids / render_ids_lds)
+// The slab forms (rt_kernels_shard.h), one unit per pass: the same form table, the kernels taking FeatureSlabArgs.
+const void* features_shard_kernel(const FeaturePlan& P);        // rt_k_features_shard.hip
+const void* features_chain_shard_kernel(const FeaturePlan& P);  // rt_k_features_chain_shard.hip
+const void* ids_shard_kernel(const FeaturePlan& P);             // rt_k_ids_shard.hip
+// rt_k_features_shard.hip: the record merge queued on `stream` (G: shard 0's geometry); a hipError_t as int.
+int assemble_records_launch(const rtd::SlabGeometry& G, const void* d_slabs, void* d_image, void* stream);
 }  // namespace rt

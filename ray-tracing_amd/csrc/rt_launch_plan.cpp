@@ -197,10 +197,12 @@ int plan_launch(const WorldShape& W, const rt_render_params& p, int span_first, 
   return RT_OK;
 }
 
-int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out, bool chain) {
+int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out, bool chain,
+                  long long slab_blocks) {
   FeaturePlan P;
   rt_launch_info& I = P.info;
-  const long long blocks = (long long)((p.width + 7) / 8) * ((p.height + 7) / 8);  // (8x8 pixel blocks, one per wave)
+  // (8x8 pixel blocks, one per wave: the image's, or the blocks of a shard's tiles for a slab pass)
+  const long long blocks = slab_blocks >= 0 ? slab_blocks : (long long)((p.width + 7) / 8) * ((p.height + 7) / 8);
   if ((long long)p.width * p.height >= (1ll << 32)) return invalid("image too large for 32-bit pixel ids");
   const bool ref_cull = (p.flags & RT_FLAG_REFERENCE_CULL) || W.far_boxes;
   // The 4-wide walk for the worlds the spheres variant renders over a 4-wide tree (the reference-cull flag asks

@@ -120,7 +120,10 @@ constexpr int kFeatBlocksPerCU = 8;  // global-memory forms: RT_BLOCK-thread blo
 // packed_keys, waves (the LDS-staged form's), wide, and leaf_stop, trav_stop and box_first (FeaturePlan::leaf_stop).
 // `chain`: a specular-chain pass (rt.h rt_render_features_chain; kernels: rt_k_features_chain.hip): the same forms,
 // the LDS-staged one at 3 waves per SIMD where RTAMD_WAVES does not say otherwise.
+// `slab_blocks` >= 0: a pass over a shard's slab (rt.h rt_render_features_shard_async): the same forms for the same
+// world, work_items and the grid from the blocks of the shard's tiles (rt_layout.h SlabGeometry::blocks; 0: the
+// shard owns no tile and nothing is launched).
 int plan_features(const WorldShape& W, const rt_render_params& p, const LaunchKnobs& K, FeaturePlan& out,
-                  bool chain = false);
+                  bool chain = false, long long slab_blocks = -1);
 
 }  // namespace rt

@@ -1,9 +1,13 @@
 // rt_layout.h — the device copy of a scene as the host prepares it and the kernels read it: node-id
-// tags, stack bounds, kernel feature flags and variants, the device material record. Plain C++ (no
-// HIP), shared by the host-only scene preparation (rt_prepare.cpp, also built under ASan/UBSan) and
-// the kernels (rt_device.h).
+// tags, stack bounds, kernel feature flags and variants, the device material record, the record slab's
+// block map. Plain C++ in a CPU build (the host-only scene preparation, rt_prepare.cpp, and the stand-alone
+// checks are also built under ASan/UBSan); under hipcc it includes the HIP runtime header, in every unit
+// alike, so that the few helpers the kernels call (RT_HD) are host and device functions everywhere.
 #pragma once
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 
 #include "rt.h"
 #include "rt_wide.h"
@@ -138,6 +142,113 @@ inline long long launch_units(long long items, long long tail_items, int chunk) 
   return items + (items < tail_items ? items : tail_items) * (chunk - 1);
 }
 
+// The inline helpers below that kernels call: host and device in every unit hipcc compiles (the HIP runtime
+// header is included above for it), plain inline functions in a CPU build. (Undefined at the end of this header.)
+#if defined(__HIPCC__)
+#define RT_HD __host__ __device__ __forceinline__
+#else
+#define RT_HD inline
+#endif
+
+// Unsigned 32-bit division by an invariant divisor d >= 1 (Granlund & Montgomery): with
+// l = ceil(log2 d) and m = floor(2^32 (2^l - d) / d) + 1, n / d = (t + ((n - t) >> s1)) >> s2 for
+// every 32-bit n, t = umulhi(m, n), s1 = min(l, 1), s2 = max(l - 1, 0). One multiply and a few
+// shifts instead of the software division a `/` on the device becomes.
+struct UDiv {
+  uint32_t m;
+  int s1, s2;
+};
+inline UDiv make_udiv(uint32_t d) {
+  int l = 0;
+  while ((1ull << l) < d) ++l;
+  const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
+  return UDiv{(uint32_t)m, l < 1 ? l : 1, l > 1 ? l - 1 : 0};
+}
+RT_HD uint32_t udiv(uint32_t n, UDiv d) {
+#ifdef __HIP_DEVICE_COMPILE__
+  const uint32_t t = __umulhi(d.m, n);
+#else  // (the host evaluates the work decomposition for the launch-geometry check)
+  const uint32_t t = (uint32_t)(((uint64_t)d.m * n) >> 32);
+#endif
+  return (t + ((n - t) >> d.s1)) >> d.s2;
+}
+
+// The record slab of shard (tile, shard_rank, shard_count) of a frame (rt.h rt_render_features_shard_async): one
+// 64-byte record per slab pixel, in the slot rt_kernels.h's assemble reads,
+//   slot = lt * tile^2 + (by * bpr + bx) * 64 + (row & 7) * 8 + (px & 7),
+// lt the shard's lt-th tile (image tile shard_rank + lt * shard_count), (bx, by) the pixel's 8x8 block inside the
+// tile, bpr = tile / 8. So slot >> 6 numbers the slab's 8x8 blocks, tile-major and row-major inside a tile, and
+// slot & 63 is the pixel's place in its block: block b is what one wave of a slab pass folds, lane l its pixel
+// (l & 7, l >> 3), stored at slot b * 64 + l. A shard's tiles inside the image are its first `owned_tiles`, so its
+// first `blocks` blocks are the ones with image tiles; the slab's other blocks are padding.
+struct SlabGeometry {
+  int W, H, tile, tiles_x, bpr;
+  int shard_rank, shard_count;
+  long long tiles_total, slab;      // (FrameGeometry's: image tiles, slab pixels of every shard)
+  long long owned_tiles, blocks;    // this shard's tiles inside the image, and their 8x8 blocks
+  UDiv div_bpt, div_bpr, div_tiles_x;  // by bpr * bpr, bpr, tiles_x
+};
+// What a record slab's callers reject of the frame and shard fields (null: fine): what rt_shard_geometry rejects of
+// width, height, tile, shard_rank and shard_count, and a slab of 2^32 slots or more (block and slot ids are 32-bit).
+inline const char* slab_params_error(const rt_render_params* p) {
+  if (p->width <= 0 || p->height <= 0) return "width and height must be positive";
+  if ((long long)p->width * p->height >= (1ll << 32)) return "a frame of 2^32 pixels or more";
+  const int tile = p->tile ? p->tile : kDefaultTile;
+  if (tile <= 0 || tile % 8 || tile > 256) return "tile must be a multiple of 8 in [8, 256]";
+  if (p->shard_count < 0 || (p->shard_count > 0 && (p->shard_rank < 0 || p->shard_rank >= p->shard_count)) ||
+      (p->shard_count <= 1 && p->shard_rank != 0))
+    return "bad shard_rank/shard_count";
+  const long long tx = (p->width + tile - 1) / tile, ty = (p->height + tile - 1) / tile;
+  const long long shards = p->shard_count > 0 ? p->shard_count : 1;
+  if ((tx * ty + shards - 1) / shards * tile * tile >= (1ll << 32)) return "a slab of 2^32 slots or more";
+  return nullptr;
+}
+inline SlabGeometry slab_geometry(const rt_render_params* p) {
+  const FrameGeometry g = frame_geometry(p);
+  SlabGeometry G{};
+  G.W = p->width, G.H = p->height, G.tile = g.tile, G.tiles_x = g.tiles_x, G.bpr = g.tile >> 3;
+  G.shard_count = p->shard_count > 0 ? p->shard_count : 1;
+  G.shard_rank = p->shard_rank;
+  G.tiles_total = g.tiles_total, G.slab = g.slab;
+  G.owned_tiles = G.shard_rank < g.tiles_total ? (g.tiles_total - G.shard_rank + G.shard_count - 1) / G.shard_count : 0;
+  G.blocks = G.owned_tiles * G.bpr * G.bpr;
+  G.div_bpt = make_udiv((uint32_t)(G.bpr * G.bpr)), G.div_bpr = make_udiv((uint32_t)G.bpr);
+  G.div_tiles_x = make_udiv((uint32_t)G.tiles_x);
+  return G;
+}
+// (The third statement of the slab map: rt_kernels.h's work_pixel is the same map per slab pixel with the render's
+// launch constants, its `assemble` the inverse. The render kernels keep theirs; a change to one is a change to all.)
+// Block b (< 2^32 / 64) of the slab -> the image pixel of its lane 0; false: a block of a tile past the image's
+// last. Lane l's pixel is (px0 + (l & 7), row0 + (l >> 3)), in the image where px < W and row < H.
+RT_HD bool slab_block(const SlabGeometry& G, uint32_t b, int& px0, int& row0) {
+  const uint32_t lt = udiv(b, G.div_bpt), blk = b - lt * (uint32_t)(G.bpr * G.bpr);
+  const long long gt = (long long)G.shard_rank + (long long)lt * G.shard_count;
+  if (gt >= G.tiles_total) return false;
+  const uint32_t ty = udiv((uint32_t)gt, G.div_tiles_x), tx = (uint32_t)gt - ty * (uint32_t)G.tiles_x;
+  const uint32_t by = udiv(blk, G.div_bpr), bx = blk - by * (uint32_t)G.bpr;
+  px0 = (int)(tx * (uint32_t)G.tile + bx * 8u);
+  row0 = (int)(ty * (uint32_t)G.tile + by * 8u);
+  return true;
+}
+// Slab slot -> image pixel index row * W + px, or -1 for a padding slot.
+RT_HD long long slab_slot_pixel(const SlabGeometry& G, uint32_t slot) {
+  int px0, row0;
+  if (!slab_block(G, slot >> 6, px0, row0)) return -1;
+  const int px = px0 + (int)(slot & 7u), row = row0 + (int)((slot >> 3) & 7u);
+  return px < G.W && row < G.H ? (long long)row * G.W + px : -1;
+}
+// Image pixels the shard owns (host: a loop over its tiles).
+inline long long slab_owned_pixels(const SlabGeometry& G) {
+  long long n = 0;
+  for (long long lt = 0; lt < G.owned_tiles; ++lt) {
+    const long long gt = G.shard_rank + lt * G.shard_count;
+    const long long x0 = (gt % G.tiles_x) * G.tile, y0 = (gt / G.tiles_x) * G.tile;
+    const long long w = G.W - x0 < G.tile ? G.W - x0 : G.tile, h = G.H - y0 < G.tile ? G.H - y0 : G.tile;
+    n += w * h;
+  }
+  return n;
+}
+
 // Device material: the rt_material record plus whether its texture tree reads (u, v).
 struct DMat {
   int type;
@@ -146,5 +257,7 @@ struct DMat {
   int needs_uv;
   int _pad;
 };
+
+#undef RT_HD
 
 }  // namespace rtd

@@ -856,14 +856,14 @@ int chain_check(const rt_feature_chain* ch) {
 }
 
 int features_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p, bool chain,
-                  rt_launch_info* out, int32_t* out_extra) {
+                  rt_launch_info* out, int32_t* out_extra, long long slab_blocks = -1) {
   if (!desc || !p || !out || cu_count < 1) return invalid("null argument");
   if (p->width <= 0 || p->height <= 0) return invalid("width and height must be positive");
   rt::PreparedScene S;
   int rc = rt::prepare_scene(desc, upload_flags, S);
   if (rc) return rc;
   rt::FeaturePlan P;
-  if ((rc = rt::plan_features(rt::world_shape(S, cu_count), *p, rt::read_knobs(), P, chain))) return rc;
+  if ((rc = rt::plan_features(rt::world_shape(S, cu_count), *p, rt::read_knobs(), P, chain, slab_blocks))) return rc;
   *out = P.info;
   if (out_extra) {
     const int32_t extra[RT_FEATURES_PLAN_EXTRA] = {P.n_items, P.entries, P.n_leaves, P.pk, P.leaf_stop};
@@ -1095,12 +1095,16 @@ int features_check(const rt_ctx* c, const rt_camera* cam, const rt_render_params
 // to 0, the kernel. The counter is the ctx's work counter, so the pass takes its place in the ctx's launch
 // order: after the previous tier-B launch (ev_done), and the next one waits for it. `ch`: a chain pass (the same
 // plan, rt_k_features_chain.hip's kernels, its counts zeroed in the ctx's buffer); null: a first-hit pass.
+// `G`: the pass over a shard's slab (rt_render_features_shard_async): the slab forms of the same kernels
+// (rt_kernels_shard.h), d_sums the slab; a shard that owns no tile queues everything but the kernel.
 int launch_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int first, int n, int accumulate,
-                    double* d_sums, hipStream_t st, const rt_feature_chain* ch = nullptr) {
+                    double* d_sums, hipStream_t st, const rt_feature_chain* ch = nullptr, const SlabGeometry* G = nullptr) {
   rt::FeaturePlan P;
-  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P, ch != nullptr);
+  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P, ch != nullptr, G ? G->blocks : -1);
   if (rc) return rc;
-  const void* fn = ch ? rt::features_chain_kernel(P) : rt::features_kernel(P);
+  const void* fn = G    ? (ch ? rt::features_chain_shard_kernel(P) : rt::features_shard_kernel(P))
+                   : ch ? rt::features_chain_kernel(P)
+                        : rt::features_kernel(P);
   if (ch && (rc = grow(c, c->fc_counts, 3 * sizeof(unsigned long long)))) return rc;
   if (ch && !c->ev_fc) HIPCHK(hipEventCreateWithFlags(&c->ev_fc, hipEventDisableTiming));
   if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
@@ -1127,16 +1131,18 @@ int launch_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, 
   const int lds = P.info.dyn_lds_bytes;
   if (lds) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   int n_items = P.n_items, entries = P.entries, n_leaves = P.n_leaves;
-  // (the global-memory kernels take the first alone; a first-hit kernel the FeatureArgs at the head of `CA`)
-  void* args[] = {ch ? (void*)&CA : (void*)&A, &n_items, &entries, &n_leaves};
-  HIPCHK(hipLaunchKernel(fn, dim3(P.info.grid), dim3(P.info.block), args, (size_t)lds, st));
+  // (the global-memory kernels take the first alone; a first-hit kernel the FeatureArgs at the head of `CA`, a
+  // slab kernel of either pass the FeatureSlabArgs)
+  FeatureSlabArgs SA{CA, G ? *G : SlabGeometry{}};
+  void* args[] = {G ? (void*)&SA : ch ? (void*)&CA : (void*)&A, &n_items, &entries, &n_leaves};
+  if (!G || G->blocks > 0) HIPCHK(hipLaunchKernel(fn, dim3(P.info.grid), dim3(P.info.block), args, (size_t)lds, st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_done, st));
   c->last_feature = P.info;
   if (ch) {
     HIPCHK(hipEventRecord(c->ev_fc, st));
     c->fc_made = true;
-    c->fc_samples = (int64_t)p->width * p->height * n;
+    c->fc_samples = (G ? (int64_t)slab_owned_pixels(*G) : (int64_t)p->width * p->height) * n;
   }
   return RT_OK;
 }
@@ -1221,12 +1227,13 @@ int ids_check(const rt_ctx* c, const rt_camera* cam, const rt_render_params* p, 
 // launch_features for an id pass: the same plan (a staged pass at the chain passes' 3 waves per SIMD: its kernels
 // hold the same walk and chain state), rt_k_ids.hip's kernel, the same place in the ctx's launch order. One kernel
 // for both modes: without a chain it runs with max_bounces = 0 and counts nothing.
+// `G`: over a shard's slab, as launch_features.
 int launch_ids(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* ch, int first, int n,
-               int accumulate, rt_id_record* d_recs, hipStream_t st) {
+               int accumulate, rt_id_record* d_recs, hipStream_t st, const SlabGeometry* G = nullptr) {
   rt::FeaturePlan P;
-  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P, true);
+  int rc = rt::plan_features(c->shape, *p, rt::read_knobs(), P, true, G ? G->blocks : -1);
   if (rc) return rc;
-  const void* fn = rt::ids_kernel(P);
+  const void* fn = G ? rt::ids_shard_kernel(P) : rt::ids_kernel(P);
   if (ch && (rc = grow(c, c->fc_counts, 3 * sizeof(unsigned long long)))) return rc;
   if (ch && !c->ev_fc) HIPCHK(hipEventCreateWithFlags(&c->ev_fc, hipEventDisableTiming));
   if (st != c->last_stream) HIPCHK(hipStreamWaitEvent(st, c->ev_done, 0));
@@ -1253,15 +1260,16 @@ int launch_ids(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const
   const int lds = P.info.dyn_lds_bytes;
   if (lds) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   int n_items = P.n_items, entries = P.entries, n_leaves = P.n_leaves;
-  void* args[] = {&CA, &n_items, &entries, &n_leaves};  // (the global-memory kernels take the first alone)
-  HIPCHK(hipLaunchKernel(fn, dim3(P.info.grid), dim3(P.info.block), args, (size_t)lds, st));
+  FeatureSlabArgs SA{CA, G ? *G : SlabGeometry{}};
+  void* args[] = {G ? (void*)&SA : (void*)&CA, &n_items, &entries, &n_leaves};  // (the global-memory kernels take the first alone)
+  if (!G || G->blocks > 0) HIPCHK(hipLaunchKernel(fn, dim3(P.info.grid), dim3(P.info.block), args, (size_t)lds, st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_done, st));
   c->last_feature = P.info;
   if (ch) {
     HIPCHK(hipEventRecord(c->ev_fc, st));
     c->fc_made = true;
-    c->fc_samples = (int64_t)p->width * p->height * n;
+    c->fc_samples = (G ? (int64_t)slab_owned_pixels(*G) : (int64_t)p->width * p->height) * n;
   }
   return RT_OK;
 }
@@ -1393,6 +1401,78 @@ int rt_last_feature_launch(rt_ctx* c, rt_launch_info* out) {
   if (!c || !out) return invalid("null argument");
   *out = c->last_feature;
   return RT_OK;
+}
+
+// ------------------------------------------------------------------ sharded feature and ID passes (rt.h)
+namespace {
+// The slab passes' argument checks, before any HIP call; the ctx last, as features_check. What the image-order
+// entries reject other than shard_count > 1, the chain's when there is one, and the shard geometry's.
+int features_shard_check(const char* what, const rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
+                         const rt_feature_chain* ch, int first, int n, const void* d_slab) {
+  const std::string w = std::string(what) + ": ";
+  if (ch) {
+    const int rc = chain_check(ch);
+    if (rc) {  // (chain_check names the chain pass)
+      const std::string msg = rt::last_error();
+      const size_t colon = msg.find(": ");
+      return invalid(w + (colon == std::string::npos ? msg : msg.substr(colon + 2)));
+    }
+  }
+  if (!cam || !p || !d_slab) return invalid(w + "null argument");
+  if (const char* bad = slab_params_error(p)) return invalid(w + bad);
+  if (p->rng_mode != RT_RNG_PHILOX) return invalid(w + "tier B only (RT_RNG_PHILOX)");
+  if (p->flags & RT_FLAG_SHARED_LIBM) return invalid(w + "RT_FLAG_SHARED_LIBM is a tier-A flag");
+  if (first < 0 || n < 1 || (long long)first + n > INT32_MAX)
+    return invalid(w + "needs first_sample >= 0, n_samples >= 1 and first_sample + n_samples <= INT32_MAX");
+  if (!c) return invalid(w + "null ctx");
+  if (!c->has_scene) {
+    rt::set_error(w + "no scene uploaded");
+    return RT_E_STATE;
+  }
+  return RT_OK;
+}
+}  // namespace
+
+int rt_render_features_shard_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                                   int first_sample, int n_samples, int accumulate, double* d_slab_sums, void* stream) {
+  int rc = features_shard_check("rt_render_features_shard_async", c, cam, p, chain, first_sample, n_samples, d_slab_sums);
+  if (rc) return rc;
+  const SlabGeometry G = slab_geometry(p);
+  DEVICE_SCOPE(c->device);
+  return launch_features(c, cam, p, first_sample, n_samples, accumulate, d_slab_sums, (hipStream_t)stream, chain, &G);
+}
+
+int rt_render_ids_shard_async(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_feature_chain* chain,
+                              int first_sample, int n_samples, int accumulate, rt_id_record* d_slab_records, void* stream) {
+  int rc = features_shard_check("rt_render_ids_shard_async", c, cam, p, chain, first_sample, n_samples, d_slab_records);
+  if (rc) return rc;
+  const SlabGeometry G = slab_geometry(p);
+  DEVICE_SCOPE(c->device);
+  c->allocs = 0;
+  rc = launch_ids(c, cam, p, chain, first_sample, n_samples, accumulate, d_slab_records, (hipStream_t)stream, &G);
+  c->id_allocs = c->allocs;
+  return rc;
+}
+
+int rt_assemble_records_async(rt_ctx* c, const rt_render_params* p, const void* d_slabs, void* d_image, void* stream) {
+  if (!p || !d_slabs || !d_image) return invalid("rt_assemble_records_async: null argument");
+  if (const char* bad = slab_params_error(p)) return invalid(std::string("rt_assemble_records_async: ") + bad);
+  if (!c) return invalid("rt_assemble_records_async: null ctx");
+  SlabGeometry G = slab_geometry(p);
+  G.shard_rank = 0;
+  DEVICE_SCOPE(c->device);  // (the caller's current device may be another ctx's)
+  const int e = rt::assemble_records_launch(G, d_slabs, d_image, stream);
+  if (e) return hip_fail((hipError_t)e, "rt_assemble_records_async launch");
+  return RT_OK;
+}
+
+// Internal (rt_internal.h; no device needed): the plan a slab pass of shard (p->tile, p->shard_rank, p->shard_count)
+// would launch with.
+int rt_internal_features_shard_plan(const rt_scene_desc* desc, uint32_t upload_flags, int cu_count, const rt_render_params* p,
+                                    int chain, rt_launch_info* out, int32_t* out_extra) {
+  if (!p) return invalid("null argument");
+  if (const char* bad = slab_params_error(p)) return invalid(std::string("rt_internal_features_shard_plan: ") + bad);
+  return features_plan(desc, upload_flags, cu_count, p, chain != 0, out, out_extra, slab_geometry(p).blocks);
 }
 
 int rt_debug_wide_keys(rt_ctx* c, int out[4]) {

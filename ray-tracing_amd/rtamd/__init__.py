@@ -242,6 +242,8 @@ EXPORTED = [
     "rt_render_features_chain", "rt_render_features_chain_async", "rt_last_feature_chain",
     "rt_render_ids", "rt_render_ids_async", "rt_ids_fold_host", "rt_ids_resolve", "rt_ids_matte_host", "rt_ids_matte",
     "rt_ids_matte_async", "rt_ids_preview_host", "rt_ids_preview", "rt_ids_preview_async",
+    "rt_render_features_shard_async", "rt_render_ids_shard_async", "rt_assemble_records_async",
+    "rt_assemble_records_host",
 ]
 
 # The feature-guided denoiser's flags (rt.h)
@@ -400,6 +402,12 @@ def lib() -> C.CDLL:
             "rt_ids_preview": (I, [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_uint8)]),
             "rt_ids_preview_async": (I, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
             "rt_internal_ids_allocs": (I, [C.c_void_p]),
+            "rt_render_features_shard_async": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(rt_feature_chain),
+                                                   I, I, I, C.c_void_p, C.c_void_p]),
+            "rt_render_ids_shard_async": (I, [C.c_void_p, P(rt_camera), P(rt_render_params), P(rt_feature_chain), I, I,
+                                              I, C.c_void_p, C.c_void_p]),
+            "rt_assemble_records_async": (I, [C.c_void_p, P(rt_render_params), C.c_void_p, C.c_void_p, C.c_void_p]),
+            "rt_assemble_records_host": (I, [P(rt_render_params), C.c_void_p, C.c_void_p]),
             "rt_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8), P(rt_denoise_stats)]),
             "rt_internal_denoise_host": (I, [P(rt_denoise_params), P(D), P(D), P(D), P(D), P(C.c_uint8),
                                              P(rt_denoise_stats), P(D)]),
@@ -948,6 +956,33 @@ class Context:
                                          int(accumulate), C.c_void_p(d_records), C.c_void_p(stream or None)),
                "rt_render_ids_async")
 
+    def render_features_shard_async(self, cam, params, d_slab_sums: int, first_sample: int = 0,
+                                    n_samples: Optional[int] = None, accumulate: bool = False, stream: int = 0,
+                                    chain: Optional["rt_feature_chain"] = None):
+        """rt_render_features_shard_async: the first-hit pass (with a `chain`, the specular-chain pass) over the slab of
+        shard (params.tile, params.shard_rank, params.shard_count), queued on `stream` into device memory: slab_pixels
+        records of 8 doubles in slab order (`shard_pixel_map`), padding slots untouched."""
+        n = params.spp if n_samples is None else n_samples
+        _check(lib().rt_render_features_shard_async(self._h, C.byref(cam), C.byref(params),
+                                                    C.byref(chain) if chain is not None else None, int(first_sample),
+                                                    int(n), int(accumulate), C.c_void_p(d_slab_sums),
+                                                    C.c_void_p(stream or None)), "rt_render_features_shard_async")
+
+    def render_ids_shard_async(self, cam, params, d_slab_records: int, first_sample: int = 0,
+                               n_samples: Optional[int] = None, chain: Optional["rt_feature_chain"] = None,
+                               accumulate: bool = False, stream: int = 0):
+        """rt_render_ids_shard_async: the material-ID pass over the shard's slab (slab_pixels records of 64 bytes)."""
+        n = params.spp if n_samples is None else n_samples
+        _check(lib().rt_render_ids_shard_async(self._h, C.byref(cam), C.byref(params),
+                                               C.byref(chain) if chain is not None else None, int(first_sample), int(n),
+                                               int(accumulate), C.c_void_p(d_slab_records), C.c_void_p(stream or None)),
+               "rt_render_ids_shard_async")
+
+    def assemble_records_async(self, params, d_slabs: int, d_image: int, stream: int = 0):
+        """rt_assemble_records_async: params.shard_count slabs of 64-byte records (rank-major) -> [H][W] records."""
+        _check(lib().rt_assemble_records_async(self._h, C.byref(params), C.c_void_p(d_slabs), C.c_void_p(d_image),
+                                               C.c_void_p(stream or None)), "rt_assemble_records_async")
+
     def id_matte(self, records, ids, pixels: Optional[int] = None, d_out_cov: int = 0, d_out_u8: int = 0,
                  stream: int = 0):
         """rt_ids_matte: `id_matte` on this ctx's device, bit for bit: (coverage, bytes) of host records, blocking.
@@ -1332,6 +1367,26 @@ def assemble_host(slabs: np.ndarray, params: rt_render_params) -> np.ndarray:
         ok = m >= 0
         img[m[ok]] = slabs[r][ok]
     return img.reshape(H, W, 3)
+
+
+def assemble_records_host(slabs: np.ndarray, params: rt_render_params) -> np.ndarray:
+    """rt_assemble_records_host: the shards' record slabs, (shards, slab_pixels, 8) float64 or (shards, slab_pixels) of
+    ID_DTYPE, merged into (H, W, 8) or (H, W) on the host; padding slots are not read."""
+    slabs = np.ascontiguousarray(slabs)
+    W, H = params.width, params.height
+    shards, slab = max(1, params.shard_count), shard_geometry(params)[2]
+    if slabs.dtype == ID_DTYPE:
+        shape, out_shape = (shards, slab), (H, W)
+    elif slabs.dtype == np.float64:
+        shape, out_shape = (shards, slab, RT_FEATURE_DOUBLES), (H, W, RT_FEATURE_DOUBLES)
+    else:
+        raise RTError("assemble_records_host: slabs must be float64 feature sums or ID_DTYPE records")
+    if slabs.shape != shape:
+        raise RTError(f"assemble_records_host: slabs must have shape {shape}, got {slabs.shape}")
+    out = np.zeros(out_shape, dtype=slabs.dtype)
+    _check(lib().rt_assemble_records_host(C.byref(params), C.c_void_p(slabs.ctypes.data), C.c_void_p(out.ctypes.data)),
+           "rt_assemble_records_host")
+    return out
 
 
 from .progressive import (ProgressiveFrame, ShardFrame, ShardedProgressiveFrame, adapt_decide,  # noqa: E402

@@ -647,6 +647,9 @@ class ShardedProgressiveFrame:
         self.slab_pixels = self.frames[0].slab_pixels
         self.root = self.ctxs[0]  # (assembles: local mode's first context, or rank 0's)
         self.active_pixels = self.width * self.height
+        self.cam = cam
+        self._feature_slabs = None  # (render_features: one [slab, 8] float64 tensor per local shard, kept for `into`)
+        self._feature_kept = None   # (... and (their chain, the end of their sample range))
 
     @classmethod
     def restore(cls, ctxs, blob: bytes, moments: Optional[np.ndarray] = None, *, world: Optional[int] = None,
@@ -697,8 +700,8 @@ class ShardedProgressiveFrame:
         dist.all_gather(parts, host)
         return torch.stack(parts).to(slab.device)
 
-    def _assemble(self, slabs):
-        """[world, slab, 3] uint8 or float64 slabs -> numpy [H, W, 3] on the root (None elsewhere)."""
+    def _assemble_device(self, slabs):
+        """[world, slab, 3] uint8 or float64 slabs -> a [H, W, 3] tensor on the root device (None off the root)."""
         torch = self._torch()
         if self.rank != 0:
             return None
@@ -709,7 +712,12 @@ class ShardedProgressiveFrame:
         else:
             self.root.assemble_linear_async(self.p, slabs.data_ptr(), img.data_ptr())
         torch.cuda.synchronize(slabs.device)
-        return img.cpu().numpy()
+        return img
+
+    def _assemble(self, slabs):
+        """[world, slab, 3] uint8 or float64 slabs -> numpy [H, W, 3] on the root (None elsewhere)."""
+        img = self._assemble_device(slabs)
+        return None if img is None else img.cpu().numpy()
 
     def _sum_counts(self, dicts, keys) -> dict:
         """The shards' exact counts added (rt.h: frame and adapt stats merge by plain addition)."""
@@ -869,6 +877,105 @@ class ShardedProgressiveFrame:
         if k is not None:
             parts.append(np.ascontiguousarray(k, dtype="<i4").tobytes())
         return b"".join(parts)
+
+    # ---- guides, mattes and the denoised preview (rt.h: sharded feature and ID passes)
+    def _record_pass(self, slabs, accumulate: bool, first_sample: int, n_samples: Optional[int], chain, ids: bool):
+        """One slab pass per local shard into `slabs` (zeroed [slab, ...] tensors of 64-byte records on the shards'
+        devices), the gather, and rt_assemble_records_async at the root: the [H, W, ...] tensor there, None elsewhere."""
+        torch = self._torch()
+        n = self.spp if n_samples is None else int(n_samples)
+        for f, t in zip(self.frames, slabs):
+            st = torch.cuda.current_stream(t.device).cuda_stream  # (after the tensor's fill, before the copies below)
+            call = f._ctx.render_ids_shard_async if ids else f._ctx.render_features_shard_async
+            call(self.cam, f.params, t.data_ptr(), first_sample, n, chain=chain, accumulate=accumulate, stream=st)
+        for t in slabs:
+            torch.cuda.current_stream(t.device).synchronize()
+        gathered = self._all_slabs(slabs)
+        if self.rank != 0:
+            return None
+        gathered = gathered.contiguous()
+        img = torch.zeros((self.height, self.width) + tuple(gathered.shape[2:]), dtype=gathered.dtype,
+                          device=gathered.device)
+        self.root.assemble_records_async(self.p, gathered.data_ptr(), img.data_ptr(),
+                                         stream=torch.cuda.current_stream(gathered.device).cuda_stream)
+        torch.cuda.current_stream(gathered.device).synchronize()
+        return img
+
+    def render_features(self, first_sample: int = 0, n_samples: Optional[int] = None, chain=None, into=None):
+        """The feature sums of samples first_sample .. first_sample + n_samples - 1 (default: the frame's spp), every
+        shard rendering its slab (`Context.render_features_shard_async`; with `chain`, the specular-chain pass), as
+        a [H, W, 8] float64 torch tensor on the root device (None on the other ranks): byte for byte what
+        `Context.render_features` gives for the whole image. The object keeps the shards' slabs; `into` (the
+        tensor an earlier call returned, or True) accumulates this range onto them, so a progressive caller adds
+        [k0, k1) without rendering or gathering the earlier samples again. Without `into` the slabs start from 0.
+        `into` is a request, not a buffer: the sums are the kept slabs', whatever tensor is passed. It needs kept
+        slabs of the same chain whose samples end where this range begins; anything else raises RTError, since
+        the sum would be of no sample range."""
+        torch = self._torch()
+        accumulate = into is not None and into is not False
+        n = self.spp if n_samples is None else int(n_samples)
+        key = None if chain is None else (chain.max_bounces, chain.flags, chain.max_fuzz)
+        if accumulate:
+            if self._feature_slabs is None:
+                raise _rt.RTError("render_features: `into` without an earlier call whose slabs it could add to")
+            if self._feature_kept != (key, int(first_sample)):
+                raise _rt.RTError("render_features: `into` must continue the kept slabs: the same chain, and "
+                                  f"first_sample = {self._feature_kept[1]}, where their samples end")
+        else:
+            self._feature_slabs = [torch.zeros((f.slab_pixels, _rt.RT_FEATURE_DOUBLES), dtype=torch.float64,
+                                               device=f"cuda:{f._ctx.device}") for f in self.frames]
+        self._feature_kept = (key, int(first_sample) + n)  # (the kept slabs' chain and the end of their samples)
+        return self._record_pass(self._feature_slabs, accumulate, int(first_sample), n, chain, ids=False)
+
+    def render_ids(self, first_sample: int = 0, n_samples: Optional[int] = None, chain=None):
+        """The material-ID records of the same samples, every shard rendering its slab, as an (H, W) numpy array of
+        ID_DTYPE (None off the root): byte for byte what `Context.render_ids` gives for the whole image."""
+        torch = self._torch()
+        slabs = [torch.zeros((f.slab_pixels, 64), dtype=torch.uint8, device=f"cuda:{f._ctx.device}")
+                 for f in self.frames]
+        img = self._record_pass(slabs, False, int(first_sample), n_samples, chain, ids=True)
+        if img is None:
+            return None
+        return img.cpu().numpy().view(_rt.ID_DTYPE).reshape(self.height, self.width)
+
+    def denoise(self, feature_sums, feature_samples: int, rgb: bool = True, linear: bool = True, **params):
+        """(rgb8[H,W,3] | None, linear[H,W,3] | None, stats dict) of the frame's current preview through the
+        feature-guided denoiser, what `ProgressiveFrame.denoise` returns for the unsharded frame at the same
+        chunks_done: the shards' previews are assembled on the root device, and their error maps when the frame
+        tracks moments and has two chunks, and rt_denoise_async filters the assembled image there (no halo
+        exchange between shards); only the result is copied back. `feature_sums`: [H, W, 8], e.g. what
+        `render_features` returned (a torch tensor, moved to the root device if it is elsewhere, or a numpy array).
+        The counts rt_denoise_async does not report are taken on the device, by rt.h's rule: a pixel is valid when
+        its three channels are finite; kernel_ms is the filter's time by device events. The frame is left as it
+        is: a `resolve` after it reports what it would have reported. (None, None, {}) on a rank other than 0."""
+        torch = self._torch()
+        p = _rt.make_denoise_params(self.width, self.height, int(feature_samples), **params)
+        with_se = self.tracks_moments and self.chunks_done >= 2
+        lins = self._slabs_of(lambda f: f.slab_tensor(torch.float64), lambda f, t: f.resolve_into(None, t))
+        d_lin = self._assemble_device(self._all_slabs(lins))
+        d_se = None
+        if with_se:
+            ses = self._slabs_of(lambda f: f.slab_tensor(torch.float64), lambda f, t: f.error_into(t))
+            d_se = self._assemble_device(self._all_slabs(ses))
+        if self.rank != 0:
+            return None, None, {}
+        dev = d_lin.device
+        if isinstance(feature_sums, np.ndarray):
+            feature_sums = torch.from_numpy(_doubles(feature_sums, (self.height, self.width, _rt.RT_FEATURE_DOUBLES)))
+        d_feat = feature_sums.to(dev).contiguous()
+        d_out = torch.zeros((self.height, self.width, 3), dtype=torch.float64, device=dev)
+        d_rgb = torch.zeros((self.height, self.width, 3), dtype=torch.uint8, device=dev) if rgb else None
+        st = torch.cuda.current_stream(dev)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(st)
+        self.root.denoise_async(p, d_lin.data_ptr(), d_se.data_ptr() if with_se else 0, d_feat.data_ptr(),
+                                d_out.data_ptr(), d_rgb.data_ptr() if rgb else 0, stream=st.cuda_stream)
+        t1.record(st)
+        was, now = torch.isfinite(d_lin).all(dim=-1), torch.isfinite(d_out).all(dim=-1)
+        n_in, n_out, n_fill = (int(x) for x in torch.stack([(~was).sum(), (~now).sum(), (~was & now).sum()]).cpu())
+        stats = {"pixels": self.width * self.height, "invalid_in": n_in, "invalid_out": n_out, "filled": n_fill,
+                 "kernel_ms": t0.elapsed_time(t1)}
+        return (d_rgb.cpu().numpy() if rgb else None), (d_out.cpu().numpy() if linear else None), stats
 
     @classmethod
     def resume(cls, ctxs, blob: bytes, *, world: Optional[int] = None, rank: Optional[int] = None,

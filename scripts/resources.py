@@ -1,6 +1,6 @@
 """Per-kernel register / scratch / occupancy table of the render kernels (hipcc -Rpass-analysis).
 
-    python scripts/resources.py [filter] [--tu spheres|spheres_global|spheres_packed|count_packed|cornell|full|full_dark|features|features_chain|denoise|ids|render ...] [-- extra hipcc flags]
+    python scripts/resources.py [filter] [--tu spheres|spheres_global|spheres_packed|count_packed|cornell|full|full_dark|features|features_chain|denoise|ids|features_shard|features_chain_shard|ids_shard|render ...] [-- extra hipcc flags]
 
 The translation units (rt_k_*.hip, rt_render.hip) compile in parallel; --tu limits the run to some.
 """
@@ -18,7 +18,7 @@ def main():
         i = args.index("--")
         args, extra = args[:i], args[i + 1:]
     tus = ["spheres", "spheres_global", "spheres_packed", "count_packed", "cornell", "full", "full_dark", "features", "features_chain",
-           "denoise", "ids", "render"]
+           "denoise", "ids", "features_shard", "features_chain_shard", "ids_shard", "render"]
     if "--tu" in args:
         i = args.index("--tu")
         sel = [a for a in args[i + 1:] if a in tus]
